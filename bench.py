@@ -11,7 +11,9 @@ counts RK4 steps: value = ranks x members x nodes x steps x 1000 / time.  Ranks 
 (weak scaling, no data-path collective): rank 0 broadcasts the packed constants once (RCCL),
 outlet rows are gathered at the end.
 
-Prints ONE JSON line on rank 0 (see the task contract): value = total mesh-node-steps/s.
+Prints ONE JSON line on rank 0 (see the task contract): value = total mesh-node-steps/s.  A plain run sets up,
+warms up, times --steps launches and prints that line; --full adds the code-object figures of the timed kernel
+(roofline, valu_fp64) and the extra measurements (CPU baseline, accuracy, other sizes and steppers).
 """
 import argparse
 import json
@@ -394,10 +396,59 @@ def executed_step_mix(loop, kname, dev_defines, compile_variant):
     return mix, note
 
 
+def code_object_figures(args, mech, dev, ens, defines, code_blob, kname, kernel_ms):
+    """--full: the timed launches priced against the MI355X peaks from the code object that ran
+    -> (digests for the line's `config`, its `roofline` and `valu_fp64` entries)."""
+    from rmt_app_amd import isa
+    from rmt_app_amd.n2 import compile_mechanism
+    E, n_nodes = args.members, args.nodes
+    bytes_per_node_step = 2*(mech.S + 2)*8
+    # kernel_ms = average launch duration in the timed region (HIP events on the launch stream)
+    achieved = (E*n_nodes*RK4_PER_STEP*bytes_per_node_step/1e9)/(kernel_ms/1e3)
+    # fp64 VALU instructions per node-step: counted in the step loop of the code object that was
+    # launched (llvm-objdump), not a constant; HBM traffic: the tracked PMC record of THIS code object
+    ist = isa.kernel_stats(code_blob, kname)
+    loop, mix_note = executed_step_mix(
+        ist.get("step_loop") or ist["whole"], kname, dev.defines,
+        lambda extra: compile_mechanism(mech, n_nodes, block=args.block, npt=args.npt, lds_state=args.lds,
+                                        defines={**defines, **ens.member_defines, **extra}, E=E,
+                                        extra_opts=args.copt))
+    f64_ops = loop["valu_f64"]/float(dev.npt)
+    traffic, traffic_src = tracked_traffic(ist["kernel_digest"], E, n_nodes)
+    valu_rate = E*n_nodes*RK4_PER_STEP*f64_ops/(kernel_ms/1e3)
+    return {"kernel_digest": ist["kernel_digest"], "code_object_digest": ist["digest"]}, {
+        # contract form: ALGORITHMIC bytes (SURVEY 8(d): 2(S+2)8 B per node-step) / kernel time against the
+        # HBM peak.  The state stays on chip for all steps of a launch, so this is NOT the kernel's HBM
+        # use (that is `measured_hbm_GBs` = PMC traffic / kernel time, ~1000x smaller) and 1/frac is not
+        # bandwidth headroom: the limiter is fp64 VALU issue, priced in `valu_fp64`.
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved/HBM_PEAK_GBS, "achieved_is": "algorithmic bytes / kernel time",
+                     "limiter": "valu_fp64", "limiter_frac": valu_rate/(FP64_PEAK_TOPS*1e12),
+                     "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE+WRITE_SIZE)",
+                     "traffic_source": traffic_src,
+                     "measured_hbm_GBs": (traffic/1e9)/(kernel_ms/1e3) if traffic else None,
+                     "kernel_ms": kernel_ms, "bytes_per_node_step": bytes_per_node_step},
+        # the real ceiling of this kernel: fp64 vector issue; ops/node-step = v_*_f64 instructions in
+        # the step loop of the launched code object / nodes per lane (rmt_app_amd/isa.py)
+        "valu_fp64": {"ops_per_node_step": f64_ops, "ops_source": "llvm-objdump of code object %s, step loop "
+                      "of %s: %d v_*_f64 of %d VALU, %d scratch, %d lane moves%s" % (
+                          ist["digest"], kname, loop["valu_f64"], loop["valu"], loop["scratch"], loop["lane_moves"],
+                          mix_note),
+                      "achieved_Tops": valu_rate/1e12, "peak_Tops": FP64_PEAK_TOPS,
+                      "frac": valu_rate/(FP64_PEAK_TOPS*1e12),
+                      # what this instruction mix could reach with no stall at all, from the measured issue costs
+                      # of profiles/round2_issue_model.md (2 waves/SIMD: 4.8 cycles per fp64 VALU instruction,
+                      # ~3 per other VALU instruction, against the 4 cycles `peak_Tops` assumes)
+                      "mix_ceiling_frac": 4.0*loop["valu_f64"]/(4.8*loop["valu_f64"]
+                                                                + 3.0*(loop["valu"] - loop["valu_f64"])),
+                      "mix_ceiling_source": "profiles/round2_issue_model.md (tools/microbench/issue.hip)"},
+    }
+
+
 def prebuild(members=MEMBERS_PER_GPU, n_nodes=N_NODES):
-    """Cross-compile (hipRTC; no GPU) every code object the default `python bench.py` run loads, into the in-tree
-    cache that travels with the repository - called by __graft_entry__.build(), so the bench on a fresh GPU box
-    spends its time measuring, not JIT-compiling.  Mirrors the device constructions below one by one."""
+    """Cross-compile (hipRTC; no GPU) every code object `python bench.py --full` loads (a plain run: the first), into
+    the in-tree cache - called by __graft_entry__.build(), so the bench spends its time measuring, not JIT-compiling.
+    Mirrors the device constructions below one by one."""
     import inputs as INP
     from rmt_app_amd import plan
     from rmt_app_amd.ensemble import DistributedEnsemble
@@ -453,7 +504,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--members", type=int, default=MEMBERS_PER_GPU, help="reactors per GPU")
     ap.add_argument("--nodes", type=int, default=N_NODES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also price the launched code object (roofline, valu_fp64) and run the extra measurements "
+                         "(CPU baseline, accuracy, other sizes and steppers; N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the extra measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step (state.npy, [members][V][nodes], rank 0's members) "
+                         "and the outlet rows of every member (outlet.npy, [members][V]) to DIR, float64")
     ap.add_argument("--mode", default="auto", choices=["auto", "reg", "mem"])
     ap.add_argument("--block", type=int, default=None)
     ap.add_argument("--npt", type=int, default=None)
@@ -555,29 +612,20 @@ def main():
     outlet = ens.gather_outlet(y)          # [world*E][V] on rank 0: the sweep's result table
     if rank == 0:
         assert outlet.shape == (total, mech.V) and bool(torch.isfinite(outlet).all())
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "state.npy"),
+                    y.reshape(E, mech.V, n_nodes).cpu().numpy().astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, "outlet.npy"), outlet.cpu().numpy().astype(np.float64))
 
     code_blob = bytes(dev._code.raw)
     dev.close()
     if rank == 0:
-        from rmt_app_amd import isa
         node_steps = world*E*n_nodes*args.steps*RK4_PER_STEP
         value = node_steps/tmax
-        bytes_per_node_step = 2*(mech.S + 2)*8
-        # kernel_ms = average launch duration in the timed region (HIP events on the launch stream)
-        achieved = (E*n_nodes*RK4_PER_STEP*bytes_per_node_step/1e9)/(kernel_ms/1e3)
-        # fp64 VALU instructions per node-step: counted in the step loop of the code object that was
-        # launched (llvm-objdump), not a constant; HBM traffic: the tracked PMC record of THIS code object
         kname = "rmt_n2_rk4_%s" % ("mem" if args.mode == "mem" else
                                    ("reg" if n_nodes <= dev.block*dev.npt else "chain"))
-        ist = isa.kernel_stats(code_blob, kname)
-        loop, mix_note = executed_step_mix(
-            ist.get("step_loop") or ist["whole"], kname, dev.defines,
-            lambda extra: compile_mechanism(mech, n_nodes, block=args.block, npt=args.npt, lds_state=args.lds,
-                                            defines={**defines, **ens.member_defines, **extra}, E=E,
-                                            extra_opts=args.copt))
-        f64_ops = loop["valu_f64"]/float(dev.npt)
-        traffic, traffic_src = tracked_traffic(ist["kernel_digest"], E, n_nodes)
-        valu_rate = E*n_nodes*RK4_PER_STEP*f64_ops/(kernel_ms/1e3)
+        extras = args.full and not args.no_cpu_baseline and world == 1
         line = {
             "metric": "mesh-node-steps/s (6-sp DME dynamic model); max |\u0394MoFri| vs SciPy ref",
             "value": value, "unit": "mesh-node-steps/s", "n_gpus": world, "steps": args.steps,
@@ -591,38 +639,16 @@ def main():
                        "members_per_gpu": E, "nodes": n_nodes, "integrator": "rk4",
                        "parallelism": "ensemble-dp%d" % world,
                        "extras": ("full (cpu_baseline, accuracy, single reactor, mesh sweep, adaptive, time to "
-                                  "solution)" if (world == 1 and not args.no_cpu_baseline) else
-                                  "throughput line only (the extra measurements run at N = 1)"),
+                                  "solution)" if extras else
+                                  "throughput line only (the extra measurements run with --full at N = 1)"),
                        "kernel": "%s block=%d npt=%d lds_state=%d" % (kname, dev.block, dev.npt, dev.lds_state),
-                       "kernel_digest": ist["kernel_digest"], "code_object_digest": ist["digest"],
                        "cache_fallbacks_rank0": fallbacks},
-            # contract form: ALGORITHMIC bytes (2(S+2)8 B per node-step) / kernel time against the
-            # HBM peak.  The state stays on chip for all steps of a launch, so this is NOT the kernel's HBM
-            # use (that is `measured_hbm_GBs` = PMC traffic / kernel time, ~1000x smaller) and 1/frac is not
-            # bandwidth headroom: the limiter is fp64 VALU issue, priced in `valu_fp64`.
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved/HBM_PEAK_GBS, "achieved_is": "algorithmic bytes / kernel time",
-                         "limiter": "valu_fp64", "limiter_frac": valu_rate/(FP64_PEAK_TOPS*1e12),
-                         "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE+WRITE_SIZE)",
-                         "traffic_source": traffic_src,
-                         "measured_hbm_GBs": (traffic/1e9)/(kernel_ms/1e3) if traffic else None,
-                         "kernel_ms": kernel_ms, "bytes_per_node_step": bytes_per_node_step},
-            # the real ceiling of this kernel: fp64 vector issue; ops/node-step = v_*_f64 instructions in
-            # the step loop of the launched code object / nodes per lane (rmt_app_amd/isa.py)
-            "valu_fp64": {"ops_per_node_step": f64_ops, "ops_source": "llvm-objdump of code object %s, step loop "
-                          "of %s: %d v_*_f64 of %d VALU, %d scratch, %d lane moves%s" % (
-                              ist["digest"], kname, loop["valu_f64"], loop["valu"], loop["scratch"], loop["lane_moves"],
-                              mix_note),
-                          "achieved_Tops": valu_rate/1e12, "peak_Tops": FP64_PEAK_TOPS,
-                          "frac": valu_rate/(FP64_PEAK_TOPS*1e12),
-                          # what this instruction mix could reach with no stall at all, from the measured issue costs
-                          # of profiles/round2_issue_model.md (2 waves/SIMD: 4.8 cycles per fp64 VALU instruction,
-                          # ~3 per other VALU instruction, against the 4 cycles `peak_Tops` assumes)
-                          "mix_ceiling_frac": 4.0*loop["valu_f64"]/(4.8*loop["valu_f64"]
-                                                                    + 3.0*(loop["valu"] - loop["valu_f64"])),
-                          "mix_ceiling_source": "profiles/round2_issue_model.md (tools/microbench/issue.hip)"},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            digests, figures = code_object_figures(args, mech, dev, ens, defines, code_blob, kname, kernel_ms)
+            line["config"].update(digests)
+            line.update(figures)
+        if extras:
             line["cpu_baseline"] = cpu_baseline(mech, rows, IV, n_nodes)
             line["cpu_baseline"]["reference_python"] = reference_cpu_rate(n_nodes)
             line["accuracy"] = accuracy_vs_scipy_reference()

@@ -5,7 +5,7 @@ L=gpurun_out/r3af/log.txt
 : > $L
 for o in "" "-mllvm -enable-post-misched=0" "-mllvm -amdgpu-schedule-relaxed-occupancy=1" "-mllvm -amdgpu-schedule-metric-bias=0" "-mllvm -amdgpu-schedule-metric-bias=30" "-mllvm -amdgpu-disable-unclustered-high-rp-reschedule=1" "-mllvm -amdgpu-enable-rewrite-partial-reg-uses=1" "-mllvm -misched-cluster=0"; do
 echo "### copt: $o" >> $L
-timeout -k 10 200 python bench.py --no-cpu-baseline --steps 5 --copt "$o" 2>&1 | grep -v amdgpu.ids | python -c "
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 5 --copt "$o" 2>&1 | grep -v amdgpu.ids | python -c "
 import sys, json
 for l in sys.stdin:
     try:

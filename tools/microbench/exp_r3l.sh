@@ -12,8 +12,8 @@ for l in sys.stdin:
     except Exception:
         print(l[:300].rstrip())
 " >> $L; }
-run python bench.py --no-cpu-baseline --steps 5
-run python bench.py --no-cpu-baseline --steps 5 --lds 1
-run python bench.py --no-cpu-baseline --steps 5 --lds 0 --define RMT_KCACHE=1 --define RMT_KCACHE_STATIC=1 --define RMT_KCACHE_GEN=0
-run python bench.py --no-cpu-baseline --steps 5 --lds 1 --define RMT_KCACHE=1 --define RMT_KCACHE_STATIC=1 --define RMT_KCACHE_GEN=0
+run python bench.py --full --no-cpu-baseline --steps 5
+run python bench.py --full --no-cpu-baseline --steps 5 --lds 1
+run python bench.py --full --no-cpu-baseline --steps 5 --lds 0 --define RMT_KCACHE=1 --define RMT_KCACHE_STATIC=1 --define RMT_KCACHE_GEN=0
+run python bench.py --full --no-cpu-baseline --steps 5 --lds 1 --define RMT_KCACHE=1 --define RMT_KCACHE_STATIC=1 --define RMT_KCACHE_GEN=0
 cat $L

@@ -9,6 +9,6 @@ run python tools/run_one.py rk45 dme_nb 1024 256 8e-3 512 2 auto RMT_RK45_LDS=2
 run python tools/run_one.py rk45 dme_nb 1024 256 8e-3 512 2 auto RMT_RK45_LDS=2 RMT_RK45_CALL_FLAGS=1
 run python tools/run_one.py rk45 dme_nb 1024 256 8e-3 512 2 auto RMT_RK45_LDS=2
 run python tools/run_one.py rk45 dme_nb 1024 256 8e-3 512 2 auto RMT_RK45_LDS=2 RMT_RK45_CALL_FLAGS=1
-run python bench.py --no-cpu-baseline --steps 5 --block 1024 --npt 1 --lds 1 --define RMT_KCACHE=1 --define RMT_KCACHE_GEN=0
-run python bench.py --no-cpu-baseline --steps 5 --block 1024 --npt 1 --lds 2
+run python bench.py --full --no-cpu-baseline --steps 5 --block 1024 --npt 1 --lds 1 --define RMT_KCACHE=1 --define RMT_KCACHE_GEN=0
+run python bench.py --full --no-cpu-baseline --steps 5 --block 1024 --npt 1 --lds 2
 cat $L

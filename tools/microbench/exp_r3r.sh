@@ -13,6 +13,6 @@ for l in sys.stdin:
         print(l[:300].rstrip())
 " >> $L; }
 for k in 1 4 8 16; do
-run python bench.py --no-cpu-baseline --steps 5 --define RMT_KC_REFRESH=$k
+run python bench.py --full --no-cpu-baseline --steps 5 --define RMT_KC_REFRESH=$k
 done
 cat $L

@@ -13,9 +13,9 @@ for l in sys.stdin:
     except Exception:
         print(l[:300].rstrip())
 " >> $L; }
-run python bench.py --no-cpu-baseline --steps 5 --define RMT_NODE_RCP_MERGE=0
-run python bench.py --no-cpu-baseline --steps 5
+run python bench.py --full --no-cpu-baseline --steps 5 --define RMT_NODE_RCP_MERGE=0
+run python bench.py --full --no-cpu-baseline --steps 5
 export RMT_TIMING_GEN_CHEAP=1
-run python bench.py --no-cpu-baseline --steps 5
+run python bench.py --full --no-cpu-baseline --steps 5
 run python tools/run_one.py rk4 dme_nb 1024 256 1000 512 2 auto
 cat $L

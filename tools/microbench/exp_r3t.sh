@@ -13,6 +13,6 @@ for l in sys.stdin:
         print(l[:300].rstrip())
 " >> $L; }
 run python -m pytest tests/test_gpu_kcache.py tests/test_gpu_parity.py -x -q
-run python bench.py --no-cpu-baseline --steps 5
-run python bench.py --no-cpu-baseline --steps 5
+run python bench.py --full --no-cpu-baseline --steps 5
+run python bench.py --full --no-cpu-baseline --steps 5
 cat $L

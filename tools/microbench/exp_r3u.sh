@@ -12,7 +12,7 @@ for l in sys.stdin:
         print(l[:300].rstrip())
 " >> $L; }
 for i in 1 2; do
-run python bench.py --no-cpu-baseline --steps 8
-run python bench.py --no-cpu-baseline --steps 8 --define RMT_KC_PAD=0
+run python bench.py --full --no-cpu-baseline --steps 8
+run python bench.py --full --no-cpu-baseline --steps 8 --define RMT_KC_PAD=0
 done
 cat $L

@@ -6,9 +6,9 @@ tag=${1:-prof}
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/$tag
 mkdir -p $out
-python bench.py > $out/bench_default.json
+python bench.py --full > $out/bench_default.json
 echo "bench line written"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --no-cpu-baseline > $out/bench_prof.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --full --no-cpu-baseline > $out/bench_prof.json
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python bench.py --no-cpu-baseline > /dev/null
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python bench.py --no-cpu-baseline > /dev/null
 echo "traffic passes done"

@@ -31,6 +31,8 @@
  *   rmt_n1_profile      - PackedBedHomoReactorClass.runN1 / modelEquationN1 (pbHomoReactor.py:2694-3314):
  *                         the steady-state model N1, integrated along z* for E reactors at once
  *                         (one per lane) with the same Rosenbrock scheme; SURVEY.md 8(f) rank 1.
+ *                         Models M7 / M1 (PackedBedReactorClass.runM3 / runM1, pbReactor.py:1170-1575, 141-547)
+ *                         use it too, with code objects generated for them (RMT_SS_MODEL).
  *   (model M2)          - PackedBedReactorClass.runM2 / modelEquationM2 (pbReactor.py:552-1165) uses the
  *                         SAME entry points: the generated prelude selects its node functions
  *                         (RMT_MODEL 2), state rows are kmol/m^3 and K; SURVEY.md 8(f) rank 3.
@@ -153,7 +155,10 @@ int rmt_n2_ros4(rmt_n2_handle* h, void* y_inout, double t0, double t1, double rt
 /* (tuning experiments: the environment variable RMT_N2_ROS4_CHUNKS=c overrides the number of chunks rmt_n2_ros4 cuts a
  * reactor into, 1 = one workgroup per reactor; unset = the library's estimate) */
 /* members1: HOST [E][16+S+NU] rows (layout M1_* in csrc/kernels/22_node_n1.inc); out: DEVICE double [E][nout][S+2]
- * (S+1 when iso-thermal) = the state at z* = k/(nout-1); stats: DEVICE [E] */
+ * (S+1 when iso-thermal) = the state at z* = k/(nout-1); stats: DEVICE [E].
+ * The same entry point drives any steady module: a code object generated with RMT_SS_MODEL 7 (model M7, runM3) or 1
+ * (model M1, runM1) reads rows of the same width in its own layout (csrc/kernels/23_node_steady.inc) and writes
+ * [E][nout][V1] scaled states, V1 = S+2 (M7) or S+3 (M1). */
 int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* out, int nout, double rtol,
                    double atol, double h0, int64_t max_steps, rmt_n2_stats* stats_out);
 /* copies the E flag words to host memory (synchronises the stream) and clears them on device */

@@ -6,7 +6,13 @@
 // same Rosenbrock(4,3) scheme is used, here with a dense (S+2)^2 finite-difference Jacobian and ONE
 // REACTOR PER LANE (an ensemble of N1 profiles); steps are clipped to the output grid.
 //   member row (doubles, host: plan.member_constants_n1): see M1_* below.
-#define RMT_V1 (RMT_S + 1 + (RMT_ISO ? 0 : 1))
+// The per-lane stepper rmt_n1_ros4 (70_n1.inc) integrates any steady model through the three functions rmt_n1_init,
+// rmt_n1_rhs and rmt_n1_rhs_jac; the generation-time define RMT_SS_MODEL picks their bodies: absent or 0 = model N1
+// (this file), 7 = model M7, 1 = model M1 (23_node_steady.inc).  Every steady model keeps the member-row width
+// 16 + S + NU, with the user parameters in the last NU columns.
+#ifndef RMT_SS_MODEL
+#define RMT_SS_MODEL 0
+#endif
 #define RMT_NM1 (16 + RMT_S + RMT_NU)
 #define M1_USER (16 + RMT_S)
 __device__ __forceinline__ void rmt_n1_user(const double* __restrict__ mr, real (&U)[RMT_NU > 0 ? RMT_NU : 1]) {
@@ -14,6 +20,8 @@ __device__ __forceinline__ void rmt_n1_user(const double* __restrict__ mr, real 
 #pragma unroll
     for (int k = 0; k < RMT_NU; ++k) U[k] = real(mr[M1_USER + k]);
 }
+#if RMT_SS_MODEL == 0
+#define RMT_V1 (RMT_S + 1 + (RMT_ISO ? 0 : 1))
 #define M1_CMAX 0
 #define M1_TF 1
 #define M1_PF 2          // = P0
@@ -52,6 +60,15 @@ __device__ __forceinline__ real rmt_n1_inv_macote(const double* __restrict__ mr,
 #else
     (void)i;
     return real(mr[M1_INV_MACOTE]);
+#endif
+}
+// initial state u(z* = 0): c_i = SpCoi0[i]/Cmax, P* = 1, theta = 0 (pbHomoReactor.py:2831-2839)
+__device__ __forceinline__ void rmt_n1_init(const double* __restrict__ mr, real (&u)[RMT_V1]) {
+#pragma unroll
+    for (int i = 0; i < RMT_S; ++i) u[i] = real(mr[M1_CIN + i]);              // :2831-2839
+    u[RMT_S] = real(1);
+#if !RMT_ISO
+    u[RMT_S + 1] = real(0);
 #endif
 }
 template <typename FL>
@@ -236,4 +253,5 @@ __device__ __forceinline__ void rmt_n1_rhs_jac(const double* __restrict__ mr, co
     }
 }
 #endif   // RMT_WITH_N1
+#endif   // RMT_SS_MODEL == 0
 

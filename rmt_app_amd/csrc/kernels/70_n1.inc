@@ -3,7 +3,8 @@
 #define RMT_ROS_GAM 0.5
 #endif
 // ===================================================================== kernel: steady-state model N1 (batched)
-// (node function rmt_n1_rhs and the M1_* row layout: see the node-physics section above)
+// (node functions rmt_n1_init / rmt_n1_rhs / rmt_n1_rhs_jac of the steady model RMT_SS_MODEL and its member-row layout:
+// see the node-physics section above)
 template <int NV>
 __device__ __forceinline__ real rmt_invert_n(real (&a)[NV][NV]) {
     real pmin = real(__builtin_inf());
@@ -42,12 +43,7 @@ extern "C" __global__ __launch_bounds__(64) void rmt_n1_ros4(
                  C41 = -112.0 / 125, C42 = -54.0 / 125, C43 = -2.0 / 5, B1 = 19.0 / 9, B2 = 0.5,
                  B3 = 25.0 / 108, B4 = 125.0 / 108, E1 = 17.0 / 54, E2 = 7.0 / 36, E4 = 125.0 / 108;
     real u[RMT_V1];
-#pragma unroll
-    for (int i = 0; i < RMT_S; ++i) u[i] = real(mr[M1_CIN + i]);              // :2831-2839
-    u[RMT_S] = real(1);
-#if !RMT_ISO
-    u[RMT_S + 1] = real(0);
-#endif
+    rmt_n1_init(mr, u);                                  // the model's state at z* = 0 (22_node_n1.inc, 23_node_steady.inc)
     rmt_flags_t flag, trial;
     rmt_flags_clear(flag);
     double z = 0.0, h = h0;

@@ -400,12 +400,14 @@ class N2Device:
                                                 float(rtol), float(atol), float(h0), int(max_steps),
                                                 C.c_void_p(self._stats.data_ptr())))
 
-    def n1_profile(self, rows1, nout, rtol, atol, h0, max_steps):
+    def n1_profile(self, rows1, nout, rtol, atol, h0, max_steps, V1=None):
         """Steady-state model N1 (needs features=("n1",)): one profile per member row of ``rows1`` (layout M1_*),
-        sampled at z* = k/(nout-1); returns the host array [E][nout][S+2] (S+1 when iso-thermal)."""
+        sampled at z* = k/(nout-1); returns the host array [E][nout][S+2] (S+1 when iso-thermal).  A module generated
+        for another steady model (RMT_SS_MODEL, steady.py) passes its own number of unknowns V1."""
         torch = self.torch
         rows1 = np.ascontiguousarray(rows1, dtype=np.float64).reshape(self.E, self.mech.row_width)
-        V1 = self.mech.S + (1 if self.mech.iso else 2)
+        if V1 is None:
+            V1 = self.mech.S + (1 if self.mech.iso else 2)
         out = torch.zeros((self.E, int(nout), V1), dtype=torch.float64, device=self.device)
         hipbind.check(hipbind.lib().rmt_n1_profile(
             self.h, rows1.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(out.data_ptr()), int(nout),

@@ -115,7 +115,10 @@ class Mechanism:
         # "M2" (dimensional dynamic model, pbReactor.py:552-1165) has no process-type key: it is
         # always non-iso-thermal; everything else on this path is the dimensionless N2/N1 pair
         self.model = "M2" if mi.get('model') == "M2" else "N2"
-        if self.model == "M2":
+        # the steady models M7 / M1 (pbReactor.py:141-547, 1170-1575) have no process-type key either: non-iso-thermal;
+        # they only use the steady kernel rmt_n1_ros4, RMT_MODEL stays 0
+        self.steady = mi.get('model') if mi.get('model') in ("M7", "M1") else None
+        if self.model == "M2" or self.steady:
             self.processType = PROCESS_SETTING['NON-ISO-THER']
         else:
             self.processType = mi['operating-conditions']['process-type']
@@ -520,6 +523,121 @@ def member_constants_n1(modelInput, mech):
     nm = dict(nm, vf=vf, SpCoi0_Set=np.array(nm["SpCoi0"], dtype=float) if fix else nm["Cmax"],
               GaMaCoTe0=(vf/zf)*(np.array(nm["SpCoi0"], dtype=float) if fix else np.repeat(nm["Cmax"], mech.S)))
     return nm, row
+
+
+def _steady_common(modelInput, mech):
+    """The scalars runM3 and runM1 share (pbReactor.py:155-238, 1189-1279)."""
+    mi = modelInput
+    if mech.steady != mi.get('model'):
+        raise ValueError("mechanism built for model %r, input is model %r" % (mech.steady, mi.get('model')))
+    P = mi['operating-conditions']['pressure']
+    T = mi['operating-conditions']['temperature']
+    ReSpec = mi['reactor']
+    ReInDi, ReLe = ReSpec['ReInDi'], ReSpec['ReLe']
+    PaDi, BeVoFr = ReSpec['PaDi'], ReSpec['BeVoFr']
+    CrSeAr = PI_CONST*(ReInDi**2)/4                                   # :184, :1218
+    GaMiVi = mi['feed']['mixture-viscosity']                          # :214, :1238
+    ergB = ((1 - BeVoFr)**2)/(BeVoFr**3)                              # :451, :1494
+    ergD = (1 - BeVoFr)/(BeVoFr**3)                                   # :453, :1496
+    named = {"P0": P, "T0": T, "ReLe": ReLe, "ReInDi": ReInDi, "CrSeAr": CrSeAr, "GaMiVi": GaMiVi,
+             "BeVoFr": BeVoFr, "PaDi": PaDi, "MoWei": np.array(mech.MW, dtype=float), "StHeRe25": mech.StHeRe25}
+    return named, ReLe/P*150*GaMiVi*ergB/(PaDi**2), ReLe/P*1.75*ergD/PaDi
+
+
+def member_constants_m7(modelInput, mech):
+    """Model M7 = runM3 (pbReactor.py:1170-1369; RHS modelEquationM3, :1371-1575): the setup block's values as named
+    reference quantities, and the packed row of the M7 body of rmt_n1_rhs (layout M7_* in
+    csrc/kernels/23_node_steady.inc): unknowns C_i/CMAX, (T - T0)/T0, P/P0 along z/ReLe."""
+    mi = modelInput
+    named, erga, ergc = _steady_common(mi, mech)
+    SpCoi0 = 1*np.array(mi['feed']['concentration'], dtype=float)     # :1227 [mol/m^3]
+    if SpCoi0.shape != (mech.S,):
+        raise ValueError("feed.concentration must have one entry per shell component")
+    SpCo0 = np.sum(SpCoi0)                                            # :1229
+    VoFlRa0 = mi['feed']['volumetric-flowrate']                       # :1224
+    InGaVe0 = VoFlRa0/(named["CrSeAr"]*named["BeVoFr"])                # :1440
+    ExHe = mi['external-heat']
+    P, T, ReLe = named["P0"], named["T0"], named["ReLe"]
+    Cmax = np.max(SpCoi0)
+    named.update(SpCoi0=SpCoi0, SpCo0=SpCo0, VoFlRa0=VoFlRa0, InGaVe0=InGaVe0, Cmax=Cmax,
+                 OvHeTrCo=ExHe['OvHeTrCo'], EfHeTrAr=ExHe['EfHeTrAr'], MeTe=ExHe['MeTe'],
+                 IV=np.concatenate([SpCoi0, [T, P]]))                 # :1244-1247
+    row = mech.new_row(mi)
+    row[0], row[1], row[2], row[3] = Cmax, T, P, SpCo0
+    row[4], row[5] = erga, ergc
+    row[6], row[7] = InGaVe0, named["BeVoFr"]
+    row[8], row[9] = ReLe/Cmax, ReLe/T
+    row[10] = ExHe['OvHeTrCo']*ExHe['EfHeTrAr']                       # Ua, :1547-1551 (the input's EfHeTrAr)
+    row[11] = ExHe['MeTe']
+    row[MEMBER_FIXED:MEMBER_FIXED + mech.S] = SpCoi0/Cmax
+    return named, row
+
+
+def member_constants_m1(modelInput, mech):
+    """Model M1 = runM1 (pbReactor.py:141-352; RHS modelEquationM1, :354-547): named reference quantities and the
+    packed row of the M1 body of rmt_n1_rhs (layout SM1_* in csrc/kernels/23_node_steady.inc): unknowns F_i/FTOT,
+    F*/F*(0), (T - T0)/T0, P/P0 along z/ReLe."""
+    mi = modelInput
+    named, erga, ergc = _steady_common(mi, mech)
+    MoFri = np.array(mi['feed']['mole-fraction'])                     # :191
+    if MoFri.shape != (mech.S,):
+        raise ValueError("feed.mole-fraction must have one entry per shell component")
+    MoFlRa = mi['feed']['molar-flowrate']                             # :193
+    MoFlRai = MoFlRa*MoFri                                            # :195
+    MoFl = MoFlRa/named["CrSeAr"]                                     # :197
+    ExHe = mi['external-heat']
+    a = 4/named["ReInDi"]                                             # :211 (EfHeTrAr overridden)
+    P, T, ReLe = named["P0"], named["T0"], named["ReLe"]
+    IV = np.zeros(mech.S + 3)                                         # :223-227
+    IV[0:mech.S] = MoFlRai
+    IV[mech.S], IV[mech.S + 1], IV[mech.S + 2] = MoFl, T, P
+    Ftot = float(np.sum(IV[0:mech.S]))
+    named.update(MoFri=MoFri, MoFlRa=MoFlRa, MoFlRai=np.array(IV[0:mech.S]), MoFl=MoFl, Ftot=Ftot,
+                 OvHeTrCo=ExHe['OvHeTrCo'], EfHeTrAr=a, MeTe=ExHe['MeTe'], IV=IV)
+    row = mech.new_row(mi)
+    row[0], row[1], row[2], row[3] = Ftot, T, P, MoFl
+    row[4], row[5] = erga, ergc
+    row[6] = named["BeVoFr"]
+    row[7], row[8], row[9] = ReLe*named["CrSeAr"]/Ftot, ReLe/MoFl, ReLe/T
+    row[10] = ExHe['OvHeTrCo']*a
+    row[11] = ExHe['MeTe']
+    row[MEMBER_FIXED:MEMBER_FIXED + mech.S] = IV[0:mech.S]/Ftot
+    return named, row
+
+
+def unscale_steady(U, named, model, S):
+    """Kernel states u (..., V1) of rmt_n1_ros4 for model M7 / M1 -> the reference's solve_ivp variables
+    ([C_i, T, P] for M7, [F_i, F*, T, P] for M1)."""
+    U = np.asarray(U, dtype=np.float64)
+    Y = np.empty_like(U)
+    T0, P0 = named["T0"], named["P0"]
+    if model == "M7":
+        Y[..., :S] = U[..., :S]*named["Cmax"]
+        Y[..., S] = U[..., S]*T0 + T0
+        Y[..., S + 1] = U[..., S + 1]*P0
+    else:
+        Y[..., :S] = U[..., :S]*named["Ftot"]
+        Y[..., S] = U[..., S]*named["MoFl"]
+        Y[..., S + 1] = U[..., S + 1]*T0 + T0
+        Y[..., S + 2] = U[..., S + 2]*P0
+    return Y
+
+
+def scale_steady(Y, named, model, S):
+    """The inverse of unscale_steady."""
+    Y = np.asarray(Y, dtype=np.float64)
+    U = np.empty_like(Y)
+    T0, P0 = named["T0"], named["P0"]
+    if model == "M7":
+        U[..., :S] = Y[..., :S]/named["Cmax"]
+        U[..., S] = (Y[..., S] - T0)/T0
+        U[..., S + 1] = Y[..., S + 1]/P0
+    else:
+        U[..., :S] = Y[..., :S]/named["Ftot"]
+        U[..., S] = Y[..., S]/named["MoFl"]
+        U[..., S + 1] = (Y[..., S + 1] - T0)/T0
+        U[..., S + 2] = Y[..., S + 2]/P0
+    return U
 
 
 def uniform_columns(rows):

@@ -4,7 +4,8 @@ result shape ``{"resModel": ..., "comTime": ...}``.
 
 Only the hot path named in BASELINE.json is implemented: ``model == "N2"`` (dynamic homogeneous
 packed-bed reactor), plus the "next" rows of SURVEY.md section 8(f): ``"N1"`` (steady state) and ``"M2"``
-(the dimensional dynamic model).  ``solver-config.ivp`` selects the device integrator: ``"hip-ros4"`` (stiff
+(the dimensional dynamic model), and the steady packed-bed models ``"M7"`` (runM3) and ``"M1"`` (runM1), which
+always use the per-lane Rosenbrock stepper of N1 whatever ``ivp`` names (steady.py).  ``solver-config.ivp`` selects the device integrator: ``"hip-ros4"`` (stiff
 Rosenbrock), ``"hip-rk4"``, ``"hip-rk45"``, ``"AM"`` (the reference's PreCorr3); ``"default"`` - LSODA
 in the reference, pbHomoReactor.py:3576, i.e. automatic stiffness detection - maps to ``"hip-auto"`` (explicit
 pair while the problem is not stiff, Rosenbrock when it is); SciPy's implicit method names map to ``"hip-ros4"``.  Any other model id raises - the reference silently returns None there
@@ -40,6 +41,13 @@ def rmtExe(modelInput):
                 from .ensemble import expand_members
                 ensemble = expand_members(modelInput, ensemble)
             resModel = run_n1(modelInput, ensemble)
+        elif modelType in ("M7", "M1"):
+            from .steady import run_steady
+            ensemble = modelInput['solver-config'].get('ensemble')
+            if ensemble is not None:
+                from .ensemble import expand_members
+                ensemble = expand_members(modelInput, ensemble)
+            resModel = run_steady(modelType, modelInput, ensemble)
         elif modelType == "M2":
             from .m2 import run_m2
             ensemble = modelInput['solver-config'].get('ensemble')
@@ -49,8 +57,9 @@ def rmtExe(modelInput):
             resModel = run_m2(modelInput, ensemble)
         else:
             raise NotImplementedError(
-                "model %r is outside the MI355X hot path (only 'N2', its steady sibling 'N1' and the "
-                "dimensional dynamic model 'M2' are built; SURVEY.md section 8)" % (modelType,))
+                "model %r is outside the MI355X hot path (only 'N2', its steady sibling 'N1', the dimensional "
+                "dynamic model 'M2' and the steady packed-bed models 'M7' and 'M1' are built; SURVEY.md section 8)"
+                % (modelType,))
         tac = timeit.default_timer()
         # the reference's comTime is (timeit.timeit()-timeit.timeit())*1000, i.e. noise
         # (rmt.py:28,67,70); here it is the real wall time in ms.

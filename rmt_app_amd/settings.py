@@ -2,7 +2,8 @@
 
 ``solverSetting``  <- PyREMOT/solvers/solSetting.py:30-106 (only the entries the N2 path reads:
                       N2.zNo/tNo/timesNo at pbHomoReactor.py:3435,3557,3561 and
-                      T1.ode-solver.PreCorr3.n at :3572).  Like the reference's dict it is a plain
+                      T1.ode-solver.PreCorr3.n at :3572; S3.timesNo and M9.zNo: the output points of
+                      the steady models M1 and M7, pbReactor.py:259, :1283).  Like the reference's dict it is a plain
                       mutable object read at run time, so ``solverSetting['N2']['zNo'] = 1024``
                       before ``rmtExe`` changes the mesh exactly as it does there.
 ``MODEL_SETTING``  <- PyREMOT/docs/modelSetting.py:10-18;  ``PROCESS_SETTING`` <- :21-23.
@@ -15,6 +16,8 @@ solverSetting = {
     "N1": {"zNo": 100},
     "N2": {"zNo": 20, "rNo": 5, "tNo": 5, "timesNo": 5},
     "S2": {"tNo": 10, "zNo": 100, "rNo": 7, "timesNo": 5},        # model M2 (solSetting.py:44-49)
+    "S3": {"timesNo": 25},                                        # model M1's output points (solSetting.py:50-52)
+    "M9": {"zNo": 30, "rNo": 1},                                  # model M7's output points (solSetting.py:53-62)
     "T1": {"ode-solver": {"PreCorr3": {"n": 100}}},
 }
 

@@ -5,7 +5,8 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting  (see SURVEY.md section 8(c), G1..G7).
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1  (see SURVEY.md
+section 8(c), G1..G7; m7 / m1: the steady models, G12).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
 """
@@ -588,6 +589,95 @@ def g_model_setting():
     print(out)
 
 
+# --------------------------------------------------------------------------- G12 (steady models M7 / M1)
+def steady_solve(mi, method=None, rtol=None, atol=None):
+    """rmtExe of a steady packed-bed model (runM3 for "M7", runM1 for "M1", pbReactor.py:141-352, 1170-1369) with the
+    solve_ivp call recorded: IV, the args tuple, the model function and sol.t / sol.y."""
+    import PyREMOT.docs.pbReactor as PBR
+    box = {"nfev": 0}
+
+    def wrapped(fun, t_span, y0, method=None, t_eval=None, args=None, **kw):
+        box.update(IV=np.array(y0, dtype=float), args=args, fun=fun)
+        if rtol is not None:
+            kw["rtol"] = rtol
+        if atol is not None:
+            kw["atol"] = atol
+        sol = REAL_SOLVE_IVP(fun, t_span, y0, method=method, t_eval=t_eval, args=args, **kw)
+        box.update(t=np.array(sol.t, dtype=float), y=np.array(sol.y, dtype=float))
+        box["nfev"] += sol.nfev
+        return sol
+
+    if method is not None:
+        mi = dict(mi)
+        mi["solver-config"] = dict(mi["solver-config"], ivp=method)
+    PBR.solve_ivp = wrapped
+    t0 = time.time()
+    try:
+        with quiet():
+            res = rmtExe(mi)
+    finally:
+        PBR.solve_ivp = REAL_SOLVE_IVP
+    box["wall"] = time.time() - t0
+    return res, box
+
+
+def steady_states(IV, Y, model):
+    """Model-function probes: the feed, three states of the run, one hot perturbed state, one with a species near
+    1e-12 of the total.  Returns (states, near_equilibrium flags)."""
+    S = len(IV) - (2 if model == "M7" else 3)
+    n = Y.shape[1]
+    ys = [IV.copy(), Y[:, 2].copy(), Y[:, n//2].copy(), Y[:, -1].copy()]
+    hot = Y[:, n//3].copy()
+    hot[:S] *= 1.0 + 0.05*np.sin(np.arange(S) + 1.0)
+    hot[S + (0 if model == "M7" else 1)] += 40.0          # T + 40 K
+    hot[-1] *= 0.97                                       # P - 3 %
+    ys.append(hot)
+    tiny = Y[:, 1].copy()
+    tiny[S - 1] = 1e-12*np.sum(tiny[:S])                  # last species (DME) at 1e-12 of the total
+    ys.append(tiny)
+    # the three run states sit close to the equilibria of methanol synthesis and dehydration (R1, R3): the rates of
+    # H2O, CH3OH, DME and the heat of reaction are differences of nearly equal terms (golden tolerance 1e-7, not 1e-11)
+    equil = np.array([False, True, True, True, False, False])
+    return np.array(ys), equil
+
+
+def g_steady(model):
+    import inputs_steady as INS
+    mi = INS.STEADY_INPUTS[(model, "dme")]()
+    res, box = steady_solve(mi)
+    rls, rsc, FunParam = box["args"]
+    setup = {"IV": box["IV"].tolist(), "const": tolist(FunParam["const"]), "ReSpec": tolist(FunParam["ReSpec"]),
+             "ExHe": tolist(FunParam["ExHe"]), "constBC1": tolist(FunParam.get("constBC1", {})),
+             "t_eval": box["t"].tolist()}
+    states, equil = steady_states(box["IV"], box["y"], model)
+    with quiet():
+        F = np.array([np.array(box["fun"](0.3, y, *box["args"]), dtype=float) for y in states])
+    rm = res["resModel"]
+    out = {"rhs_y": states, "rhs_f": F, "rhs_equil": equil,
+           "default_dataYs": np.array(rm["dataYs"], dtype=float),
+           "default_x": np.array([xy[0] for xy in rm["XYList"]], dtype=float),
+           "default_XY_y": np.array([xy[1] for xy in rm["XYList"]], dtype=float),
+           "default_dataList_y": np.array([d["y"] for d in rm["dataList"]], dtype=float),
+           "default_legends": np.array([d["leg"] for d in rm["dataList"]]),
+           "default_sol_y": box["y"], "default_nfev": np.array(box["nfev"]), "default_wall": np.array(box["wall"])}
+    # the accuracy reference: LSODA at rtol 1e-11, atol 1e-13 of each variable's own scale
+    S = len(mi["feed"]["components"]["shell"])
+    IV = box["IV"]
+    scale = np.abs(IV).copy()
+    scale[:S] = np.sum(np.abs(IV[:S]))
+    res_t, box_t = steady_solve(mi, "LSODA", 1e-11, 1e-13*scale)
+    rt = res_t["resModel"]
+    out.update(tight_dataYs=np.array(rt["dataYs"], dtype=float),
+               tight_XY_y=np.array([xy[1] for xy in rt["XYList"]], dtype=float),
+               tight_sol_y=box_t["y"], tight_nfev=np.array(box_t["nfev"]), tight_wall=np.array(box_t["wall"]))
+    name = "g12_%s" % model.lower()
+    np.savez_compressed(os.path.join(GOLD, name + ".npz"), **out)
+    with open(os.path.join(GOLD, name + "_setup.json"), "w") as f:
+        json.dump(setup, f, indent=1)
+    print("G12 %s: default nfev=%d (%.2fs), tight nfev=%d (%.2fs)" % (
+        model, box["nfev"], box["wall"], box_t["nfev"], box_t["wall"]))
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -613,6 +703,8 @@ def main(argv):
             g_model_setting()
         elif what == "m2":
             g_m2()
+        elif what in ("m7", "m1"):
+            g_steady(what.upper())
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

@@ -139,6 +139,13 @@ int rmt_n2_set_stream(rmt_n2_handle* h, void* hip_stream);
 /* replace the per-member constants (same E) without recompiling; fields that the code object's
  * prelude baked in as literals (#define RMT_MC_<FIELD>) are not affected */
 int rmt_n2_set_members(rmt_n2_handle* h, const double* members);
+/* the same, stream-ordered and without waiting: the copy is queued on the handle's stream between the launches around
+ * it, `members` must be page-locked host memory that stays untouched until the stream has passed the copy.  Forced code
+ * objects (prelude #define RMT_FORCING 1, solver-config "schedule") have their rows refreshed this way before every
+ * launch: such a row is 16 + S + NU + 4 doubles - the plan's n_user_params counts the four extra ones - the ordinary
+ * fields P0, THETA_IN and TM hold the values at the start of the launch and the tail {t_ref, d THETA_IN/dt, d P0/dt,
+ * d TM/dt} the time of that start and the slopes over the launch (kernels/11_forcing.inc). */
+int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members_pinned);
 
 int rmt_n2_rhs(rmt_n2_handle* h, double t, const void* y, void* dydt);
 int rmt_n2_rk4(rmt_n2_handle* h, void* y_inout, double t0, double dt, int64_t nsteps);

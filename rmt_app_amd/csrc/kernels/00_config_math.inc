@@ -70,7 +70,15 @@
 #ifndef RMT_NU
 #define RMT_NU 0
 #endif
+// RMT_FORCING 1 (solver-config "schedule", 11_forcing.inc): the member row grows by a tail of four doubles
+#ifndef RMT_FORCING
+#define RMT_FORCING 0
+#endif
+#if RMT_FORCING
+#define RMT_NM (16 + RMT_S + RMT_NU + 4)
+#else
 #define RMT_NM (16 + RMT_S + RMT_NU)
+#endif
 
 #define RMT_FLAG_DOMAIN 1u
 #define RMT_FLAG_DIV0 2u
@@ -97,6 +105,9 @@
 #define M_TM 14         // medium temperature, 0 = adiabatic
 #define M_CIN 16        // S inlet values SpCoi0[i]/Cmax
 #define M_USER (16 + RMT_S)   // RMT_NU user parameters (always read at run time)
+#if RMT_FORCING
+#define M_FORCE (16 + RMT_S + RMT_NU)   // t_ref, d THETA_IN/dt, d P0/dt, d TM/dt of this launch (P0, THETA_IN, TM: the values at t_ref)
+#endif
 
 typedef double preal;   // the pressure scan is always carried in fp64
 

@@ -240,6 +240,11 @@ __device__ __forceinline__ void rmt_rk4_reg_body(
 #pragma unroll 1
 #endif
         for (int s = 0; s < 4; ++s) {
+#if RMT_FORCING
+            // the forced boundary values at this stage's time t, t + h/2, t + h/2, t + h (the launch starts at t_ref)
+            rmt_forcing_stage(m, carry, members + (size_t)e * RMT_NM,
+                              members[(size_t)e * RMT_NM + M_FORCE] + ((double)step + rmt_rk4_c(s)) * h_, sh.inlet);
+#endif
             // Python-exception tests only on K1 = f(y_n); a failure inside the trial stages still
             // ends in a non-finite state (RMT_FLAG_NONFINITE)
 #if RMT_MODEL == 2
@@ -721,12 +726,18 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk4_mem(
     unsigned lflag = 0u;
     int ph = 0;
     for (long long step = 0; step < nsteps; ++step) {
+#if RMT_FORCING
+        const double tstep = members[(size_t)e * RMT_NM + M_FORCE] + (double)step * h_;     // the launch starts at t_ref
+#endif
         __syncthreads();                                 // the previous step's hand-overs have been read
         if (threadIdx.x == 0) {
             RmtCarry c0;
             rmt_carry_inlet(m, c0);
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
+#if RMT_FORCING
+                rmt_forcing_stage(m, c0, members + (size_t)e * RMT_NM, tstep + rmt_rk4_c(s) * h_, nullptr);   // each stage: its own inlet
+#endif
                 s_c.P[s] = c0.P;
 #pragma unroll
                 for (int i = 0; i < RMT_V; ++i) s_c.up[s][i] = c0.up[i];
@@ -759,6 +770,9 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk4_mem(
                 carry.P = s_c.P[s];
 #pragma unroll
                 for (int i = 0; i < RMT_V; ++i) carry.up[i] = s_c.up[s][i];
+#if RMT_FORCING
+                rmt_forcing_apply(m, members + (size_t)e * RMT_NM, tstep + rmt_rk4_c(s) * h_);     // the wall temperature of this stage
+#endif
                 if (s == 0 || RMT_CHECK_ALL_STAGES) rmt_rhs_block<RMT_NPT, true>(m, sh, ph, ys, nvalid, carry, k, flag);
                 else rmt_rhs_block<RMT_NPT, true>(m, sh, ph, ys, nvalid, carry, k, nof);
                 ph ^= 1;

@@ -95,6 +95,9 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_mem(
             rmt_carry_inlet(m, c0);
 #pragma unroll
             for (int s = 0; s < 7; ++s) {
+#if RMT_FORCING
+                rmt_forcing_stage(m, c0, members + (size_t)e * RMT_NM, t + rmt_dp_c(s) * h, nullptr);     // each stage: its own inlet
+#endif
                 s_c.P[s] = c0.P;
 #pragma unroll
                 for (int i = 0; i < RMT_V; ++i) s_c.up[s][i] = c0.up[i];
@@ -132,6 +135,9 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_mem(
                     carry.P = s_c.P[s];
 #pragma unroll
                     for (int i = 0; i < RMT_V; ++i) carry.up[i] = s_c.up[s][i];
+#if RMT_FORCING
+                    rmt_forcing_apply(m, members + (size_t)e * RMT_NM, t + rmt_dp_c(s) * h);     // the wall temperature of this stage
+#endif
                     rmt_rhs_block<1, true>(m, sh, ph, ys, valid ? 1 : 0, carry, k, trial);
                     ph ^= 1;
                     if (threadIdx.x == 0) {
@@ -411,6 +417,11 @@ __device__ __forceinline__ void rmt_rk45_onchip(
         }
 #pragma unroll 1
         for (; s <= 7; ++s) {
+#if RMT_FORCING
+            // the forced boundary values at t + c_s h (K_7 = f(t + h, y_new) is K_1 of the next step: FSAL holds, the forcing
+            // is continuous inside a launch)
+            rmt_forcing_stage(m, carry, members + (size_t)e * RMT_NM, t + rmt_dp_c(s - 1) * h, CH == 0 ? sh.inlet : nullptr);
+#endif
 #if RMT_RK45_TWO_COPIES && !RMT_CHECK_ALL_STAGES
             if (s == 7 || s == 1) { RMT_RK45_TESTED(s & 1) }               // K_7 / K_1: derivative of a visited state
             else { RMT_RK45_EVAL(s & 1, nof2) }

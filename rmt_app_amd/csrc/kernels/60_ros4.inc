@@ -342,6 +342,9 @@ __device__ __forceinline__ void rmt_ros_stage(const RmtMember& m, RmtShared& sh,
 #define RMT_ROS_SCHEME 1
 #endif
 #define RMT_RODAS_GAM 0.25
+#if RMT_FORCING && (RMT_ROS_SCHEME != 1 || RMT_ROS_QUAD)
+#error "RMT_FORCING: the stiff stepper carries the forcing in its RODAS4 one-node-per-lane form only"
+#endif
 // ---- RODAS4, node blocks outermost ---------------------------------------------------------------
 // Walking all node blocks once per stage (the layout of rmt_ros_stage) parks G_1..G_5 and the block
 // inverses in memory (5 V + V^2 doubles per node written and read back every step).  Information
@@ -351,9 +354,25 @@ __device__ __forceinline__ void rmt_ros_stage(const RmtMember& m, RmtShared& sh,
 // inverse then never leaves the registers, the G_j of the block live in LDS (5 V block doubles), and
 // a step touches memory twice per node: read y, write y_new (stage-outermost, with G_j and the
 // inverses in memory: 0.086 s for the 256 x 1024 x 0.5 s job; this order: 0.064 s).
+// RMT_FORCING (11_forcing.inc): the stepper is non-autonomous.  Stage i evaluates f(t + c_i h, Y_i) - member and inlet
+// hand-over at that time - and its right-hand side gains h d_i f_t; f_t = (f(t + del, y_n) - f(t, y_n))/del comes from ONE
+// more RHS pass per node block and step attempt, ahead of the block's stage 1, with a {pressure, upstream state} hand-over
+// of its own (slot 6: a changed p0 moves the pressure of every node downstream).  A launch whose forcing is constant (a
+// hold between two breakpoints) skips the pass and adds nothing.
+#if RMT_FORCING
+#define RMT_ROS_NCARRY 7
+#define RMT_M_ARG m_launch
+#define RMT_F_DECL , const double* __restrict__ frow, const double ft, const double fh, const bool fconst, real (&ftv)[RMT_V]
+#define RMT_F_PASS , frow, ft, fh, fconst, ftv
+#else
+#define RMT_ROS_NCARRY 6
+#define RMT_M_ARG m
+#define RMT_F_DECL
+#define RMT_F_PASS
+#endif
 struct RmtRodasCarry {
-    double P[6];
-    real up[6][RMT_V];
+    double P[RMT_ROS_NCARRY];
+    real up[RMT_ROS_NCARRY][RMT_V];
     real xc[6][RMT_V];
 };
 
@@ -375,14 +394,18 @@ struct RmtRodasCarry {
 #define RMT_ROS_TWOSTEP 1
 #endif
 template <int STAGE, int CH = 0>
-__device__ __forceinline__ void rmt_rodas_bs(const RmtMember& m, RmtShared& sh, RmtRodasCarry& rc, int& ph,
+__device__ __forceinline__ void rmt_rodas_bs(const RmtMember& RMT_M_ARG, RmtShared& sh, RmtRodasCarry& rc, int& ph,
                                              real (*s_g)[RMT_V][RMT_BLOCK], const real (&y0)[RMT_V],
                                              const bool valid, const int node, real (&a)[RMT_V][RMT_V],
                                              real (&l)[RMT_V], unsigned& mk, real (&ynew)[RMT_V],
                                              const real inv_gh, const real ih, const int sweeps,
                                              rmt_flags_t& flag, real& pivmin, const double rtol,
                                              const double atol, double& errloc, bool& bad,
-                                             RmtChainCtx* ctx, real (&nn)[RMT_V][RMT_V]) {
+                                             RmtChainCtx* ctx, real (&nn)[RMT_V][RMT_V] RMT_F_DECL) {
+#if RMT_FORCING
+    RmtMember m = m_launch;                              // the member at this stage's time t + c_i h
+    rmt_forcing_apply(m, frow, ft + rmt_rodas_t<STAGE>::c * fh);
+#endif
     const real A[6][5] = {{0, 0, 0, 0, 0}, {real(1.544), 0, 0, 0, 0},
         {real(0.9466785280815826), real(0.2557011698983284), 0, 0, 0},
         {real(3.314825187068521), real(2.896124015972201), real(0.9986419139977817), 0, 0},
@@ -434,6 +457,13 @@ __device__ __forceinline__ void rmt_rodas_bs(const RmtMember& m, RmtShared& sh, 
         rmt_rhs_block<1, true, CH>(m, sh, ph, ys, valid ? 1 : 0, carry, k, nof_stage, ctx);
 #endif
     ph ^= 1;
+#if RMT_FORCING
+    if (STAGE == 1) {                                    // ftv arrives as f(t + del, y_n); k = f(t, y_n)
+        const real idel = fconst ? real(0) : real(1.0 / (RMT_FT_FRAC * fh));
+#pragma unroll
+        for (int r = 0; r < RMT_V; ++r) ftv[r] = fconst ? real(0) : (ftv[r] - k[0][r]) * idel;
+    }
+#endif
     if (STAGE == 1) {
         rmt_noflags_t scratch_flag;
         (void)scratch_flag;
@@ -528,6 +558,13 @@ __device__ __forceinline__ void rmt_rodas_bs(const RmtMember& m, RmtShared& sh, 
     real p[RMT_V], xv[RMT_V];
 #pragma unroll
     for (int r = 0; r < RMT_V; ++r) xv[r] = valid ? k[0][r] + cg[r] : real(0);
+#if RMT_FORCING
+    if (rmt_rodas_t<STAGE>::d != 0.0 && !fconst) {       // + h d_i f_t
+        const real hd = real(rmt_rodas_t<STAGE>::d * fh);
+#pragma unroll
+        for (int r = 0; r < RMT_V; ++r) xv[r] = valid ? xv[r] + hd * ftv[r] : real(0);
+    }
+#endif
 #pragma unroll
     for (int r = 0; r < RMT_V; ++r) {
         real acc = real(0);
@@ -631,17 +668,42 @@ __device__ __forceinline__ void rmt_rodas_blocks(const RmtMember& m, RmtShared& 
                                                  const int N, const real inv_gh, const real ih,
                                                  const int sweeps, rmt_flags_t& flag, real& pivmin,
                                                  const double rtol, const double atol, double& errloc,
-                                                 bool& bad) {
+                                                 bool& bad
+#if RMT_FORCING
+                                                 , const double* __restrict__ frow, const double ft, const double fh
+#endif
+                                                 ) {
+#if RMT_FORCING
+    const bool fconst = rmt_forcing_constant(frow);
+#endif
     __syncthreads();                                     // the previous step's readers of rc are done
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int st = 0; st < 6; ++st) {
             RmtCarry c0;
+#if RMT_FORCING
+            RmtMember ms = m;                            // each stage: the inlet at its own time
+            rmt_forcing_apply(ms, frow, ft + rmt_rodas_c(st) * fh);
+            rmt_carry_inlet(ms, c0);
+#else
             rmt_carry_inlet(m, c0);
+#endif
             rc.P[st] = c0.P;
 #pragma unroll
             for (int i = 0; i < RMT_V; ++i) { rc.up[st][i] = c0.up[i]; rc.xc[st][i] = real(0); }
         }
+#if RMT_FORCING
+        {                                                // slot 6: the pass that yields f(t + del, y_n)
+            RmtCarry c0;
+            RmtMember ms = m;
+            rmt_forcing_apply(ms, frow, ft);
+            rmt_forcing_shift(ms, frow, RMT_FT_FRAC * fh);
+            rmt_carry_inlet(ms, c0);
+            rc.P[6] = c0.P;
+#pragma unroll
+            for (int i = 0; i < RMT_V; ++i) rc.up[6][i] = c0.up[i];
+        }
+#endif
     }
     __syncthreads();
     for (int base = 0; base < N; base += RMT_BLOCK) {
@@ -655,12 +717,37 @@ __device__ __forceinline__ void rmt_rodas_blocks(const RmtMember& m, RmtShared& 
 #pragma unroll
             for (int i = 0; i < RMT_V; ++i) y0[i] = ye[(size_t)i * N + node];
         }
-        rmt_rodas_bs<1>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn);
-        rmt_rodas_bs<2>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn);
-        rmt_rodas_bs<3>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn);
-        rmt_rodas_bs<4>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn);
-        rmt_rodas_bs<5>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn);
-        rmt_rodas_bs<6>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn);
+#if RMT_FORCING
+        real ftv[RMT_V];
+#pragma unroll
+        for (int i = 0; i < RMT_V; ++i) ftv[i] = real(0);
+        if (!fconst) {                                   // (workgroup-uniform) f(t + del, y_n) of this block, test-free
+            RmtMember md = m;
+            rmt_forcing_apply(md, frow, ft);
+            rmt_forcing_shift(md, frow, RMT_FT_FRAC * fh);
+            RmtCarry carry;
+            carry.P = rc.P[6];
+            real ysd[1][RMT_V], kd[1][RMT_V];
+#pragma unroll
+            for (int i = 0; i < RMT_V; ++i) { carry.up[i] = rc.up[6][i]; ysd[0][i] = y0[i]; }
+            rmt_noflags_t nof_ft;
+            rmt_rhs_block<1, true, 0>(md, sh, ph, ysd, valid ? 1 : 0, carry, kd, nof_ft);
+            ph ^= 1;
+            if (threadIdx.x == 0) {                      // (every reader of slot 6 is past the barrier inside)
+                rc.P[6] = carry.P;
+#pragma unroll
+                for (int i = 0; i < RMT_V; ++i) rc.up[6][i] = carry.up[i];
+            }
+#pragma unroll
+            for (int i = 0; i < RMT_V; ++i) ftv[i] = kd[0][i];
+        }
+#endif
+        rmt_rodas_bs<1>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn RMT_F_PASS);
+        rmt_rodas_bs<2>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn RMT_F_PASS);
+        rmt_rodas_bs<3>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn RMT_F_PASS);
+        rmt_rodas_bs<4>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn RMT_F_PASS);
+        rmt_rodas_bs<5>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn RMT_F_PASS);
+        rmt_rodas_bs<6>(m, sh, rc, ph, s_g, y0, valid, node, a, l, mk, ynew, inv_gh, ih, sweeps, flag, pivmin, rtol, atol, errloc, bad, nullptr, nn RMT_F_PASS);
         if (valid) {
 #pragma unroll
             for (int i = 0; i < RMT_V; ++i) yout[(size_t)i * N + node] = ynew[i];
@@ -751,7 +838,12 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ro
 #if RMT_ROS_SCHEME == 1
         double errloc = 0.0;
         bool bad = false;
+#if RMT_FORCING
+        rmt_rodas_blocks(m, sh, s_rc, ph, s_g, ye, YS, N, inv_gh, ih, sweeps, trial, pivmin, rtol, atol, errloc, bad,
+                         members + (size_t)e * RMT_NM, t, h);
+#else
         rmt_rodas_blocks(m, sh, s_rc, ph, s_g, ye, YS, N, inv_gh, ih, sweeps, trial, pivmin, rtol, atol, errloc, bad);
+#endif
 #else
         rmt_ros_stage<1>(m, sh, ph, ye, F, G1, G2, G3, G1, ainv, mask, coup, N, inv_gh, ih, sweeps, trial, pivmin);
         rmt_ros_stage<2>(m, sh, ph, ye, F, G1, G2, G3, G2, ainv, mask, coup, N, inv_gh, ih, sweeps, trial, pivmin);
@@ -835,6 +927,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ro
 // decision slot, every chunk reads it and applies the same controller arithmetic, so t, h and the
 // accept/reject history stay identical in all chunks without any other synchronisation.
 // A step costs 6 stage times + the pipeline skew instead of 6 C stage times.
+#if !RMT_FORCING       // (a forced run keeps a reactor on one workgroup: the host selects rmt_n2_ros4_mem)
 extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ros4_chain(
         real* __restrict__ y, real* __restrict__ work, const double* __restrict__ members, const int N,
         const int E, const int C, const int T, const int W, const double t0, const double t1,
@@ -1009,6 +1102,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ro
         for (int e2 = e; e2 < E; e2 += T) atomicOr(&flags[e2], RMT_FLAG_STEP);
     }
 }
+#endif   // !RMT_FORCING
 #endif   // RODAS4
 #endif   // !RMT_ROS_QUAD
 

@@ -302,6 +302,14 @@ extern "C" int rmt_n2_set_members(rmt_n2_handle* h, const double* members) {
     return 0;
 }
 
+extern "C" int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members) {
+    if (!h || !members) return fail("null argument");
+    ON_DEVICE(h);
+    const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
+    HIP_OK(hipMemcpyAsync(h->d_members, members, mbytes, hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
 static int ensure_work(rmt_n2_handle* h, size_t arrays, size_t extra_bytes = 0) {
     const size_t need = arrays * (size_t)h->E * h->V * h->N * h->real_size + extra_bytes;
     if (h->work_bytes >= need) return 0;

@@ -58,6 +58,7 @@ def lib():
     L.rmt_n2_set_stream.argtypes = [vp, vp]
     L.rmt_n2_set_mode.argtypes = [vp, C.c_int]
     L.rmt_n2_set_members.argtypes = [vp, C.POINTER(dbl)]
+    L.rmt_n2_set_members_async.argtypes = [vp, vp]
     L.rmt_n2_rhs.argtypes = [vp, dbl, vp, vp]
     L.rmt_n2_rk4.argtypes = [vp, vp, dbl, dbl, i64]
     L.rmt_n2_multistep.argtypes = [vp, vp, dbl, dbl, i64, C.c_int]

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import hipbind, plan
+from . import hipbind, plan, schedule
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
 
@@ -116,6 +116,35 @@ KC_REFRESH = 8          # csrc/kernels/50_rk4.inc RMT_KC_REFRESH: the cache's re
 KC_MAX_AGE = 1.3e-5     # ... RMT_KC_MAX_AGE: or sooner, so that no reference point is older than this much model time [s]
 
 
+def is_forced(defines):
+    """True for the prelude defines of a code object that evaluates a schedule (csrc/kernels/11_forcing.inc): its member
+    rows carry schedule.TAIL more doubles and none of the forced fields is baked into the kernel."""
+    return str((defines or {}).get("RMT_FORCING", "0")) == "1"
+
+
+def forced_literals(member_defines):
+    """The sweep-invariant member fields a FORCED code object may take as literals: all but the three the schedule moves
+    (no RMT_MC_* literal may freeze a forced field; the others never change between the launches of a run)."""
+    return {k: v for k, v in member_defines.items() if k not in ("RMT_MC_THETA_IN", "RMT_MC_P0", "RMT_MC_TM")}
+
+
+def forced_mode(ivp, N, block, npt, want=None):
+    """The kernel form of a forced launch, set by the HOST (rmt_n2_set_mode): the chained forms do not carry the forcing,
+    so the library's auto mode must not pick them.  "reg" (the on-chip steppers) when the reactor fits one workgroup,
+    else "mem"; the stiff stepper always runs rmt_n2_ros4_mem (any N on one workgroup).  `want`: solver-config
+    "device-mode"."""
+    if want not in (None, "auto", "reg", "mem"):
+        raise ValueError("solver-config 'device-mode' must be 'reg' or 'mem' together with 'schedule' (got %r): the "
+                         "chained kernels do not carry the forcing" % (want,))
+    if ivp == "hip-ros4":
+        return "mem"
+    fits = int(N) <= int(block)*int(npt)
+    if want == "reg" and not fits:
+        raise ValueError("solver-config 'device-mode': 'reg' holds at most %d nodes per reactor (zNo = %d)"
+                         % (int(block)*int(npt), int(N)))
+    return want if want in ("reg", "mem") else ("reg" if fits else "mem")
+
+
 def kc_period(defines, dt):
     """steps between two moves of the reference point of a caching one-workgroup RK4 stepper at step size dt (the kernel's
     own rule, csrc/kernels/50_rk4.inc rmt_rk4_reg_body)."""
@@ -144,6 +173,8 @@ def kcache_choice(mech, N, fp32, block, npt, lds_state, defines):
     not leave the room."""
     defs = dict(defines or {})
     chained = int(N) > int(block)*int(npt)
+    if is_forced(defs) and (chained or os.environ.get("RMT_N2_FORCED_PLAIN")):
+        return defs, lds_state       # (a forced reactor beyond one workgroup runs the memory-resident form, never the chain)
     key = "RMT_KCACHE_CHAIN" if chained else "RMT_KCACHE"
     geo = (int(block), int(npt))
     model = getattr(mech, "model", "N2")
@@ -216,7 +247,8 @@ def device_source(mech, members, N, fp32=False, block=None, npt=None, lds_state=
     if specialize is None:
         specialize = E >= 2
     if specialize:
-        defs.update(plan.uniform_member_defines(members, mech.S))
+        lit = plan.uniform_member_defines(members[:, :mech.row_width], mech.S)
+        defs.update(forced_literals(lit) if is_forced(defs) else lit)
     # "RMT_KCACHE": "1" (kcache_choice above, or the caller's own): the on-chip RK4 stepper caches the temperature-only
     # rate constants per node in LDS - that has to fit
     gen = plan.KCACHE_GEN[str(defs.get("RMT_KCACHE_GEN", "1"))]
@@ -285,7 +317,9 @@ class N2Device:
         members = np.ascontiguousarray(members, dtype=np.float64)
         if members.ndim == 1:
             members = members.reshape(1, -1)
-        assert members.shape[1] == mech.row_width, "member rows must hold 16 + S + NU doubles"
+        self.forced = is_forced(defines)
+        self.row_width = mech.row_width + (schedule.TAIL if self.forced else 0)
+        assert members.shape[1] == self.row_width, "member rows must hold 16 + S + NU doubles (+ 4 when forced)"
         self.E = members.shape[0]
         self.members = members
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
@@ -305,7 +339,7 @@ class N2Device:
         p.n_species, p.n_reactions, p.n_vars = mech.S, mech.R, mech.V
         p.n_nodes, p.n_members, p.fp32 = self.N, self.E, int(self.fp32)
         p.block, p.nodes_per_thread = self.block, self.npt
-        p.n_user_params = mech.NU
+        p.n_user_params = self.row_width - plan.MEMBER_FIXED - mech.S       # (a forced row's tail travels as 4 more)
         self.ros_quad = str(self.defines.get("RMT_ROS_QUAD", "0")) == "1"
         p.ros4_nodes_per_block = self.block//4 if self.ros_quad else 0
         p.code_object = C.cast(self._code, C.c_void_p)
@@ -333,13 +367,25 @@ class N2Device:
         """Replace the per-reactor constant rows (same E) without recompiling - e.g. the next
         point of a sweep.  Not available when member fields were baked into the kernel as literals
         (``specialize``): those fields would silently keep their old values."""
-        if any(k.startswith("RMT_MC_") for k in self.defines):
+        if any(k.startswith("RMT_MC_") for k in self.defines) and not self.forced:
+            # (a forced device only ever has its forced fields and the tail refreshed - those are never literals)
             raise hipbind.RmtN2Error("this kernel was specialised on its member rows "
                                      "(N2Device(..., specialize=False) keeps them run-time)")
         members = np.ascontiguousarray(members, dtype=np.float64).reshape(self.E, -1)
-        assert members.shape[1] == self.mech.row_width
+        assert members.shape[1] == self.row_width
         self.members = members
         hipbind.check(hipbind.lib().rmt_n2_set_members(self.h, members.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def set_members_async(self, members):
+        """set_members queued on the current stream without waiting for it (between two queued launches: the rows of a
+        forced run are refreshed before every launch).  Returns the page-locked staging tensor, which the caller keeps
+        alive until the stream has passed the copy."""
+        members = np.ascontiguousarray(members, dtype=np.float64).reshape(self.E, self.row_width)
+        pinned = self.torch.empty(members.shape, dtype=self.torch.float64, pin_memory=True)
+        pinned.copy_(self.torch.from_numpy(members))
+        self.members = members
+        hipbind.check(hipbind.lib().rmt_n2_set_members_async(self.h, C.c_void_p(pinned.data_ptr())))
+        return pinned
 
     def set_mode(self, mode):
         hipbind.check(hipbind.lib().rmt_n2_set_mode(self.h, {"auto": 0, "reg": 1, "mem": 2, "chain": 3}[mode]))
@@ -499,7 +545,16 @@ class AutoStepper:
     def dr(self):
         if callable(self._dr):
             self._dr = self._dr()
+            if getattr(self, "_rows", None) is not None:
+                self._dr.set_members(self._rows)
         return self._dr
+
+    def set_members(self, rows):
+        """the member rows of the next launch, for both devices (a forced run refreshes them before every launch)"""
+        self._rows = rows
+        self.d45.set_members(rows)
+        if not callable(self._dr):
+            self._dr.set_members(rows)
 
     def to_device(self, y):
         return self.d45.to_device(y)
@@ -713,18 +768,26 @@ def mechanism_for(modelInput, inputs, cfg):
 
 
 def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=None, npt=None, defines=None,
-                 features=()):
+                 features=(), forcing=None):
     """Device + initial state for the members THIS process integrates.
 
     Single process: all of ``inputs``.  As one rank of a torch.distributed job (``sync``, see
     ensemble.RankSync): the rank's contiguous block; rank 0 compiles, every rank loads the broadcast
     code object, sweep-invariant member fields agreed over all ranks become kernel literals.
-    Returns (device, named constants of the local members, local initial states [E_local][V*N])."""
+    Returns (device, named constants of the local members, local initial states [E_local][V*N]).
+    ``forcing`` (a Forcing, solver-config "schedule"): the code object is generated with RMT_FORCING, the rows get their
+    tail, and the host fixes the kernel form (forced_mode)."""
+    if forcing is not None:
+        defines = {**(defines or {}), "RMT_FORCING": "1"}
     if sync is None:
         pairs = [pack(mi, mech, zNo) for mi in inputs]
         rows = np.array([r for _, r in pairs])
         IV = plan.initial_states([nm for nm, _ in pairs], mech, zNo, init)
+        if forcing is not None:
+            rows = forcing.attach(rows, [nm for nm, _ in pairs])
         dev = device_cls()(mech, rows, zNo, fp32=fp32, block=block, npt=npt, defines=defines, features=features)
+        if forcing is not None:
+            forcing.fix_mode(dev, "hip-ros4" if "ros4" in features else "explicit")
         return dev, [nm for nm, _ in pairs], IV
     # Multi-rank: every rank-LOCAL phase (packing, the rank-0 compile inside DistributedEnsemble, loading the
     # module and allocating on the device) runs under ensemble.guarded / agree: a failure on one rank is raised
@@ -743,26 +806,33 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
             np.array([pack(mi, mech, zNo)[1] for mi in inputs[sync.lo:sync.hi]]), mech, zNo))
         defs["RMT_M2_NEWTON"] = str(sync.max_int(sweeps))
     arch = device_arch()
+    # (a forced code object takes the ensemble's uniform fields as literals except the three its schedule moves)
+    lit = forced_literals if forcing is not None else (lambda mdef: mdef)
     ens = DistributedEnsemble(
         mech, inputs, zNo, group=sync.group, device=sync.device,
-        compile_fn=lambda mdef: compile_mechanism(mech, zNo, fp32, block, npt, None, {**defs, **mdef}, arch, E_geo))
-    dev = guarded(sync, device_cls(), mech, ens.rows, zNo, fp32=fp32, block=block, npt=npt,
-                  defines={**defs, **ens.member_defines}, specialize=False, code=ens.code, features=features)
+        compile_fn=lambda mdef: compile_mechanism(mech, zNo, fp32, block, npt, None, {**defs, **lit(mdef)}, arch, E_geo))
+    rows = ens.rows if forcing is None else guarded(sync, forcing.attach, ens.rows, ens.named)
+    dev = guarded(sync, device_cls(), mech, rows, zNo, fp32=fp32, block=block, npt=npt,
+                  defines={**defs, **lit(ens.member_defines)}, specialize=False, code=ens.code, features=features)
+    if forcing is not None:
+        guarded(sync, forcing.fix_mode, dev, "hip-ros4" if "ros4" in features else "explicit")
     return dev, ens.named, ens.IV
 
 
-def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None):
+def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None, forcing=None):
     """The two devices of ivp "hip-auto" (explicit pair in its on-chip geometry, Rosenbrock family) behind one
     AutoStepper; an explicit `block` / `nodes-per-thread` of the solver-config applies to the explicit device."""
-    if block is None:
+    if block is None and forcing is not None:       # (no chained chunks: they do not carry the forcing)
+        b45, n45, d45 = rk45_geometry(mech.V, zNo, fp32, chain=False)
+    elif block is None:
         b45, n45, d45 = rk45_geometry(mech.V, zNo, fp32, E=len(inputs) if sync is None else max(sync.counts))
     else:
         b45, n45, d45 = block, npt, {}
     dev45, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=b45, npt=n45,
-                                          defines={**(defines or {}), **d45})
+                                          defines={**(defines or {}), **d45}, forcing=forcing)
     def make_ros4():
         return open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=ros4_block(mech.V, zNo, fp32),
-                            npt=1, defines=defines, features=("ros4",))[0]
+                            npt=1, defines=defines, features=("ros4",), forcing=forcing)[0]
     if sync is None:
         return AutoStepper(dev45, make_ros4), named_local, IV       # built only if the problem turns out stiff
     try:        # multi-rank: creation involves collectives and the ranks may decide differently -> build it now
@@ -812,15 +882,57 @@ def outlet_only(cfg):
     return out == 'outlet'
 
 
+class Forcing:
+    """A parsed schedule bound to one run: the launch list (output times and breakpoints), the local members' ordinary
+    rows, and the refresh of the device rows ahead of every launch (schedule.Schedule.forced_rows)."""
+
+    def __init__(self, sched, period, tNo, N, want_mode=None):
+        self.sched, self.N, self.want_mode = sched, int(N), want_mode
+        self.launches = sched.boundaries(period, tNo)
+        self.rows = self.named = None
+        self.modes = {}
+
+    def attach(self, rows, named):
+        """the local members' rows -> the forced rows of the first launch (called where the device is created)"""
+        if self.rows is None:
+            if self.sched.E != len(named):          # one rank's block of the ensemble
+                raise ValueError("solver-config 'schedule': %d member rows for a schedule of %d members"
+                                 % (len(named), self.sched.E))
+            self.rows, self.named = np.array(rows, dtype=np.float64), list(named)
+        t0, t1, _ = self.launches[0]
+        return self.sched.forced_rows(self.rows, self.named, t0, t1)
+
+    def fix_mode(self, dev, ivp):
+        mode = forced_mode(ivp, self.N, dev.block, dev.npt, self.want_mode)
+        dev.set_mode(mode)
+        self.modes["ros4" if ivp == "hip-ros4" else "explicit"] = mode
+
+    def refresh(self, dev, t0, t1, queued=False):
+        """the rows of the launch (t0, t1) onto the device; ``queued``: stream-ordered between the queued launches, returns
+        what has to stay alive until the stream got there"""
+        rows = self.sched.forced_rows(self.rows, self.named, t0, t1)
+        if queued and hasattr(dev, "set_members_async"):
+            return dev.set_members_async(rows)
+        dev.set_members(rows)
+        return None
+
+
 PIPELINE_BYTES = 1 << 30       # pinned host memory one batch of queued output intervals may hold (integrate_intervals)
 
 
-def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_interval, sync=None, outlet=False):
+def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_interval, sync=None, outlet=False,
+                        forcing=None):
     """The reference's time loop (pbHomoReactor.py:3589-3690, pbReactor.py:711-762): one device
     launch per output interval; ``on_interval(i, t1, Y_host)`` packs the end state ([E][V*zNo], or [E][V] = the
     outlet node with ``outlet``).  With ``sync`` (multi-rank ensemble) a failure on any rank is raised on every
-    rank before the next gather."""
+    rank before the next gather.
+    ``forcing`` (solver-config "schedule"): the walk goes over output times AND breakpoints (Forcing.launches; only a
+    launch that ends at an output time is packed), and the device rows are refreshed before each launch is queued."""
     tNo = len(opTSpan) - 1
+    # (t0, t1, index of the output time the launch ends at or None)
+    launches = forcing.launches if forcing is not None else \
+        [(float(opTSpan[i]), float(opTSpan[i + 1]), i + 1) for i in range(tNo)]
+    nL = len(launches)
     stats = {"steps": 0, "rhs_evals": 0, "node_steps": 0, "accepted": None, "rejected": None}
     _progress(0, tNo + 1, quiet)
     def launch(i, t0, t1):
@@ -862,22 +974,26 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     # idled - and clocked down - while the host packed: 0.18 s for the bench's 256-member sweep against 0.04 s of kernel
     # time.  The status words are sticky, so one look at the end of a batch raises what any of its launches flagged.
     # Batches are bounded by PIPELINE_BYTES of pinned memory.
-    if sync is None and ivp != "hip-auto" and tNo > 1 and getattr(y, "is_cuda", False) and hasattr(dev, "_stats"):
+    if sync is None and ivp != "hip-auto" and nL > 1 and getattr(y, "is_cuda", False) and hasattr(dev, "_stats"):
         import torch
         E_loc = y.shape[0]
         per = E_loc*(y.shape[1]//zNo if outlet else y.shape[1])*y.element_size()
-        batch = int(max(1, min(tNo, PIPELINE_BYTES//max(per, 1))))
+        batch = int(max(1, min(nL, PIPELINE_BYTES//max(per, 1))))
         check = False
-        for lo in range(0, tNo, batch):
-            hi = min(tNo, lo + batch)
-            hosts, counters, landed = [], [], []
+        for lo in range(0, nL, batch):
+            hi = min(nL, lo + batch)
+            hosts, counters, landed, staged = [], [], [], []
             for i in range(lo, hi):
-                t0, t1 = float(opTSpan[i]), float(opTSpan[i + 1])
-                _progress(i + 1, tNo + 1, quiet)
+                t0, t1, kout = launches[i]
+                _progress(i + 1, nL + 1, quiet)
+                if forcing is not None:                          # (the page-locked rows stay alive until the batch has landed)
+                    staged.append(forcing.refresh(dev, t0, t1, queued=True))
                 launch(i, t0, t1)
-                src = y.reshape(E_loc, -1, zNo)[:, :, zNo - 1] if outlet else y
-                host = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
-                host.copy_(src, non_blocking=True)               # stream-ordered: reads y before the next launch writes it
+                host = None
+                if kout is not None:
+                    src = y.reshape(E_loc, -1, zNo)[:, :, zNo - 1] if outlet else y
+                    host = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
+                    host.copy_(src, non_blocking=True)           # stream-ordered: reads y before the next launch writes it
                 hosts.append(host)
                 if adaptive:
                     c = torch.empty(dev._stats.shape, dtype=dev._stats.dtype, pin_memory=True)
@@ -893,18 +1009,24 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
                     acc, rej = raw[:, 2].copy().view(np.int64), raw[:, 3].copy().view(np.int64)
                     stats["accepted"] = acc if stats["accepted"] is None else stats["accepted"] + acc
                     stats["rejected"] = rej if stats["rejected"] is None else stats["rejected"] + rej
-                on_interval(i, float(opTSpan[i + 1]), hosts[k].numpy().astype(np.float64))
+                if hosts[k] is not None:
+                    on_interval(launches[i][2] - 1, float(opTSpan[launches[i][2]]), hosts[k].numpy().astype(np.float64))
             dev.raise_on_flags()                                  # (sticky status words: whatever a launch of the batch flagged)
-        return finish_stats(stats, ivp, n_members, tNo, zNo, dev.jacobian_evals)
+            del staged
+        return finish_stats(stats, ivp, n_members, nL, zNo, dev.jacobian_evals)
 
-    for i in range(tNo):
-        t0, t1 = float(opTSpan[i]), float(opTSpan[i + 1])
-        _progress(i + 1, tNo + 1, quiet)
+    for i in range(nL):
+        t0, t1, kout = launches[i]
+        _progress(i + 1, nL + 1, quiet)
         if sync is None:
+            if forcing is not None:
+                forcing.refresh(dev, t0, t1)
             launch(i, t0, t1)
         else:                                   # whatever goes wrong on one rank is raised on every rank
             err = None
             try:
+                if forcing is not None:
+                    forcing.refresh(dev, t0, t1)
                 launch(i, t0, t1)
             except Exception as e:              # noqa: BLE001 - re-raised on every rank by agree()
                 err = e
@@ -913,6 +1035,10 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
             st = dev.rk45_stats()
             stats["accepted"] = st["accepted"] if stats["accepted"] is None else stats["accepted"] + st["accepted"]
             stats["rejected"] = st["rejected"] if stats["rejected"] is None else stats["rejected"] + st["rejected"]
+        if kout is None:                        # a breakpoint: nothing to pack
+            continue
+        t1 = float(opTSpan[kout])
+        i = kout - 1
         if outlet:
             E_loc = y.shape[0]
             Yh = y.reshape(E_loc, -1, zNo)[:, :, zNo - 1].contiguous().cpu().numpy().astype(np.float64)
@@ -922,9 +1048,9 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     if ivp == "hip-auto":
         stats["method-per-interval"] = list(dev.choices)
     if sync is not None:
-        stats = gather_stats(stats, sync, ivp, tNo, zNo, dev.jacobian_evals)
+        stats = gather_stats(stats, sync, ivp, nL, zNo, dev.jacobian_evals)
     else:
-        stats = finish_stats(stats, ivp, n_members, tNo, zNo, dev.jacobian_evals)
+        stats = finish_stats(stats, ivp, n_members, nL, zNo, dev.jacobian_evals)
     if ivp == "hip-auto":
         stats["rhs_evals"] = dev.rhs_evals          # includes the probe and any abandoned explicit attempt
     return stats
@@ -950,20 +1076,36 @@ def run_n2(modelInput, members_inputs=None):
     from .ensemble import active_ranks, guarded
     sync = active_ranks(len(inputs)) if members_inputs else None       # one rank of a torchrun job?
     block, npt = cfg.get('block'), cfg.get('nodes-per-thread')
+    # "schedule": time-varying inlet / coolant conditions (schedule.py); absent = None = exactly the run without it
+    sched = schedule.parse(modelInput, members_inputs, ivp)
+    forcing = None
+    if sched is not None:
+        if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
+            raise NotImplementedError("solver-config 'schedule' with the stiff stepper needs a mechanism of at most 8 "
+                                      "variables per node (this one has %d): its four-lane form does not carry the "
+                                      "forcing - use ivp 'hip-rk45' or 'hip-rk4'" % mech.V)
+        forcing = Forcing(sched if sync is None else sched.members(sync.lo, sync.hi), opT, tNo, zNo,
+                          cfg.get('device-mode'))
+        if ivp == "hip-rk4" and block is None:
+            # the geometry of ONE workgroup per reactor (no chunks: the chained kernels do not carry the forcing)
+            block, npt = choose_geometry(zNo, mech.V, fp32)
     if ivp == "hip-ros4" and block is None:
         block, npt = ros4_block(mech.V, zNo, fp32), 1
     # "strict-flags": test the Python-exception conditions on every RK stage (default: stage 1 only)
     defines = {"RMT_CHECK_ALL_STAGES": "1"} if cfg.get('strict-flags') else {}
     if ivp == "hip-rk45" and block is None:
-        block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, E=len(inputs) if sync is None else max(sync.counts))
+        if forcing is not None:
+            block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, chain=False)
+        else:
+            block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, E=len(inputs) if sync is None else max(sync.counts))
         defines.update(geo_defs)
     if ivp == "hip-auto":
         dev, named_local, IV = open_auto(mech, inputs, zNo, plan.member_constants, plan.initial_state, sync, fp32,
-                                         defines, block, npt)
+                                         defines, block, npt, forcing=forcing)
     else:
         dev, named_local, IV = open_members(mech, inputs, zNo, plan.member_constants, plan.initial_state, sync,
                                             fp32=fp32, block=block, npt=npt, defines=defines,
-                                            features=("ros4",) if ivp == "hip-ros4" else ())
+                                            features=("ros4",) if ivp == "hip-ros4" else (), forcing=forcing)
     # the process that returns the results (rank 0, or the only one) packs EVERY member
     packer = sync is None or sync.rank == 0
     try:
@@ -985,11 +1127,21 @@ def run_n2(modelInput, members_inputs=None):
                     for e, pk in enumerate(pack_intervals(Yg, named, mech, 1 if outlet else zNo, t1, modelId)):
                         packs[e].append(pk)
         stats = integrate_intervals(dev, y, cfg, ivp, np.linspace(0, opT, tNo + 1), len(named_local),
-                                    zNo, quiet or not packer, on_interval, sync, outlet)
+                                    zNo, quiet or not packer, on_interval, sync, outlet, forcing)
+        if forcing is not None:
+            # which kernel forms ran: "reg" = the on-chip steppers, "mem" = the memory-resident ones; and what
+            # rmt_n2_last_geometry reports for the last launch (workgroups per reactor, teams)
+            stats["device-mode"] = dict(forcing.modes)
+            stats["launches"] = len(forcing.launches)
+            last = getattr(dev, "last", dev)
+            if hasattr(last, "last_geometry"):
+                stats["last-geometry"] = last.last_geometry()
     finally:
         dev.close()
     elapsed = np.round(timer() - start, ROUND_FUN_ACCURACY)
     resPack = {"computation-time": elapsed, "dataPack": packs[0] if packs else [], "device-stats": stats}
+    if sched is not None:
+        resPack["schedule"] = schedule.result_entry(sched, np.linspace(0, opT, tNo + 1)[1:])
     if members_inputs:
         # multi-rank: rank 0 holds the whole sweep, the other ranks None (and an empty dataPack)
         resPack["ensemble"] = [{"dataPack": p} for p in packs] if packer else None

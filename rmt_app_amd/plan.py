@@ -414,6 +414,26 @@ def member_constants(modelInput, mech, zNo):
     return named, row
 
 
+def forced_fields(rows, named, values):
+    """solver-config "schedule": write the forced boundary values [E][3] = (T_in [K], P_in [Pa], MeTe [K]) into the member
+    rows in place - THETA_IN(t) = (T_in(t) - Tf)/Tf (:4108), P0(t) = P_in(t), TM(t) = MeTe(t).  Every other field - the
+    scaling constants and the pre-combined ones - is independent of the three and stays the member's own."""
+    F = MEMBER_FIELDS
+    tf = np.array([nm["Tf"] for nm in named], dtype=np.float64)
+    values = np.asarray(values, dtype=np.float64)
+    rows[:, F["THETA_IN"]] = (values[:, 0] - tf)/tf
+    rows[:, F["P0"]] = values[:, 1]
+    rows[:, F["TM"]] = values[:, 2]
+    return rows
+
+
+def forced_slopes(named, slopes):
+    """d/dt of (THETA_IN, P0, TM) from the slopes [E][3] of (T_in, P_in, MeTe): the tail of a forced member row."""
+    tf = np.array([nm["Tf"] for nm in named], dtype=np.float64)
+    slopes = np.asarray(slopes, dtype=np.float64)
+    return np.stack([slopes[:, 0]/tf, slopes[:, 1], slopes[:, 2]], axis=1)
+
+
 def member_constants_m2(modelInput, mech, zNo):
     """Model M2 (pbReactor.py:552-700 setup, :845-1165 RHS): the packed row keeps the N2 layout
     (MEMBER_FIELDS) with the meanings listed above the M2 node functions in csrc/kernels/21_node_m2.inc."""

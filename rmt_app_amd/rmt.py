@@ -27,6 +27,9 @@ def rmtExe(modelInput):
         for c in compList:
             if c not in compdb.componentSymbolList:
                 raise Exception("Component database is not up to date!")
+        if modelType != "N2" and modelInput['solver-config'].get('schedule') is not None:
+            raise ValueError("solver-config 'schedule' (time-varying inlet / coolant conditions) is only available for "
+                             "model 'N2' (got model %r)" % (modelType,))
         if modelType == "N2":
             from .n2 import run_n2
             ensemble = modelInput['solver-config'].get('ensemble')

@@ -5,8 +5,9 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1  (see SURVEY.md
-section 8(c), G1..G7; m7 / m1: the steady models, G12).
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule  (see
+SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
+coolant conditions, G13).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
 """
@@ -678,6 +679,160 @@ def g_steady(model):
         model, box["nfev"], box["wall"], box_t["nfev"], box_t["wall"]))
 
 
+# --------------------------------------------------------------------------- G13
+# Time-varying inlet / coolant conditions (solver-config "schedule", rmt_app_amd/schedule.py).  The cases are written to
+# g13_schedule.json and read from there by the tests; nothing of the product is imported here: the piecewise-linear
+# functions are restated below.
+def _sched_abs(times, T=None, P=None, Tm=None):
+    return {"time": times, "inlet-temperature": T, "inlet-pressure": P, "medium-temperature": Tm}
+
+
+G13_STEP = lambda ts: {"time": [0.0, ts, ts, 0.4], "inlet-temperature": [523.0, 523.0, 528.0, 528.0],     # noqa: E731
+                       "inlet-pressure": [5.0e6, 5.0e6, 4.9e6, 4.9e6], "medium-temperature": [523.0, 523.0, 533.0, 533.0]}
+G13_CASES = {
+    "A": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2, "schedule": G13_STEP(0.2)},
+    "A1": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 4, "schedule": G13_STEP(0.23)},
+    "B": {"input": "dme_nb", "zNo": 20, "period": 0.3, "tNo": 6,
+          "schedule": {"time": [0.0, 0.1, 0.2, 0.3], "inlet-temperature": [523.0, 523.0, 533.0, 533.0],
+                       "medium-temperature": [523.0, 523.0, 531.0, 531.0]}},
+    "C": {"input": "dme_nb", "zNo": 600, "period": 0.06, "tNo": 3, "method": "DOP853",
+          "schedule": {"time": [0.0, 0.02, 0.04, 0.06], "inlet-temperature": [523.0, 523.0, 533.0, 533.0],
+                       "medium-temperature": [523.0, 523.0, 531.0, 531.0]}},
+    "D": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2, "members": [0, 15, 31],
+          "ensemble": {"temperature": [513.0, 516.0, 519.0, 522.0, 525.0, 528.0, 531.0, 534.0],
+                       "pressure": [4.0e6, 4.5e6, 5.0e6, 5.5e6]},
+          "schedule": {"time": [0.0, 0.2, 0.2, 0.4], "inlet-temperature": [0.0, 0.0, 5.0, 5.0],
+                       "inlet-pressure": [0.0, 0.0, -1.0e5, -1.0e5], "medium-temperature": [0.0, 0.0, 10.0, 10.0],
+                       "relative": True}},
+}
+G13_KEYS = (("inlet-temperature", "T0"), ("inlet-pressure", "P0"), ("medium-temperature", "Tm"))
+
+
+def _pw_piece(times, vals, a, b):
+    """(value at a, slope) of the linear piece of the schedule that holds over (a, b) - no breakpoint inside."""
+    T = np.asarray(times, dtype=float)
+    k = int(np.searchsorted(T, 0.5*(a + b), side="right")) - 1
+    if k >= len(T) - 1:
+        return float(vals[-1]), 0.0
+    s = (vals[k + 1] - vals[k])/(T[k + 1] - T[k])
+    return float(vals[k] + s*(a - T[k])), float(s)
+
+
+def _pw_right(times, vals, t):
+    """value at t; at a jump the one that holds from t on."""
+    T = np.asarray(times, dtype=float)
+    k = int(np.searchsorted(T, t, side="right")) - 1
+    if k >= len(T) - 1:
+        return float(vals[-1])
+    return float(vals[k] + (vals[k + 1] - vals[k])*(t - T[k])/(T[k + 1] - T[k]))
+
+
+def _g13_member_input(case, member=None):
+    mi = INP.ALL_N2_INPUTS[case["input"]](period=case["period"])
+    if member is None:
+        return mi
+    Ts, Ps = case["ensemble"]["temperature"], case["ensemble"]["pressure"]
+    T, P = Ts[member//len(Ps)], Ps[member % len(Ps)]
+    c0 = np.asarray(mi["feed"]["concentration"], dtype=float)
+    mi["operating-conditions"].update({"temperature": float(T), "pressure": float(P)})
+    mi["feed"]["concentration"] = (c0/c0.sum())*float(P)/(8.314472*float(T))       # the sweep rule of the ensemble API
+    return mi
+
+
+def g13_trajectory(case, member=None, rtol=1e-10, atol=1e-13):
+    """Whole states at the output times: SciPy on the oracle's vectorised RHS with T0, P0 and Tm as functions of t,
+    restarted at every breakpoint."""
+    from oracle import n2_oracle as O
+    mi = _g13_member_input(case, member)
+    pr = dict(O.setup_n2(mi, zNo=case["zNo"]))
+    f = O.make_rhs_vec(pr)
+    sch = case["schedule"]
+    own = {"T0": pr["T0"], "P0": pr["P0"], "Tm": pr["Tm"]}
+    vals = {}
+    for key, name in G13_KEYS:
+        if sch.get(key) is not None:
+            v = np.asarray(sch[key], dtype=float)
+            vals[name] = own[name] + v if sch.get("relative") else v
+    out_t = np.linspace(0.0, case["period"], case["tNo"] + 1)
+    marks = sorted(set(out_t.tolist()) | {b for b in sch["time"] if 0 < b < case["period"]
+                                          and np.min(np.abs(out_t - b)) > 1e-12*case["period"]})
+    y = np.array(pr["IV"], dtype=float)
+    states, nfev = [], 0
+    method = case.get("method", "LSODA")
+    for a, b in zip(marks[:-1], marks[1:]):
+        piece = {name: _pw_piece(sch["time"], v, a, b) for name, v in vals.items()}
+
+        def ft(t, yy, piece=piece, a=a):
+            for name, (v0, s) in piece.items():
+                pr[name] = v0 + s*(t - a)
+            return f(t, yy)
+        t0 = time.time()
+        sol = REAL_SOLVE_IVP(ft, (a, b), y, method=method, rtol=rtol, atol=atol)
+        if not sol.success:
+            raise RuntimeError(sol.message)
+        y = sol.y[:, -1]
+        nfev += sol.nfev
+        print("G13 %s%s: (%.4f, %.4f) nfev=%d %.0f s" % (case.get("name", ""), "" if member is None else " member %d" % member,
+                                                          a, b, sol.nfev, time.time() - t0), flush=True)
+        if np.min(np.abs(out_t - b)) <= 1e-12*case["period"]:
+            states.append(y.copy())
+    return out_t[1:], np.array(states), nfev
+
+
+def g13_probes():
+    """The reference's own modelEquationN2 with only constBC1['T0'], constBC1['P0'] and ExHe['MeTe'] replaced by the
+    forced values: five times of schedule B and two of schedule A (the pressure step), six states each."""
+    import copy
+    mi = INP.dme_notebook_input()
+    IV, params = capture(mi, 20)
+    V = params[2]["const"]["varNo"]
+    Y = np.array([IV] + synthetic_states(IV, V, 20, seed=13) + synthetic_states(IV, V, 20, seed=131)[:2])
+    assert len(Y) == 6
+    probes = [("B", t) for t in (0.0, 0.1, 0.15, 0.2, 0.3)] + [("A", t) for t in (0.1, 0.2)]
+    forced, F = [], []
+    for name, t in probes:
+        sch = G13_CASES[name]["schedule"]
+        v = {"T0": 523.0, "P0": 5.0e6, "Tm": 523.0}
+        for key, nm in G13_KEYS:
+            if sch.get(key) is not None:
+                v[nm] = _pw_right(sch["time"], sch[key], t)
+        p2 = list(params)
+        p2[2] = copy.deepcopy(params[2])
+        p2[2]["constBC1"]["T0"] = v["T0"]
+        p2[2]["constBC1"]["P0"] = v["P0"]
+        p2[2]["ExHe"]["MeTe"] = v["Tm"]
+        forced.append([v["T0"], v["P0"], v["Tm"]])
+        F.append([rhs(tuple(p2), y) for y in Y])
+    np.savez_compressed(os.path.join(GOLD, "g13_schedule_probes.npz"), y=Y, f=np.array(F), forced=np.array(forced),
+                        times=np.array([t for _, t in probes]), case=np.array([n for n, _ in probes]))
+    print("G13 probes written")
+
+
+def g_schedule(which=None):
+    with open(os.path.join(GOLD, "g13_schedule.json"), "w") as f:
+        json.dump({"cases": G13_CASES, "rtol": 1e-10, "atol": 1e-13,
+                   "reference": "SciPy LSODA (case C: DOP853) on oracle.n2_oracle.make_rhs_vec, restarted at breakpoints"},
+                  f, indent=1)
+    todo = [which] if which else ["probes", "A", "A1", "B", "C", "D"]
+    for name in todo:
+        if name == "probes":
+            g13_probes()
+            continue
+        case = dict(G13_CASES[name], name=name)
+        out = {}
+        t0 = time.time()
+        if "members" in case:
+            for m in case["members"]:
+                times, states, nfev = g13_trajectory(case, m)
+                out["states_%d" % m] = states
+        else:
+            times, states, nfev = g13_trajectory(case)
+            out["states"] = states
+        np.savez_compressed(os.path.join(GOLD, "g13_schedule_%s.npz" % name), times=times, nfev=nfev,
+                            wall_s=time.time() - t0, **out)
+        print("G13 %s written (%.0f s)" % (name, time.time() - t0))
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -705,6 +860,8 @@ def main(argv):
             g_m2()
         elif what in ("m7", "m1"):
             g_steady(what.upper())
+        elif what == "schedule" or what.startswith("schedule="):
+            g_schedule(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

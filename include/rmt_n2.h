@@ -188,6 +188,23 @@ int rmt_n2_fallbacks(rmt_n2_handle* h, uint64_t* count);
 /* timing of the last rk4/rk45/rhs launch in ms (HIP events on the handle's stream; synchronises) */
 int rmt_n2_last_kernel_ms(rmt_n2_handle* h, float* ms);
 
+/* Monitor (solver-config "monitor"): per state row y[e][v][0..N) the numbers a time series needs, reduced on the device,
+ *   out[e][v][0..5) = { y[N-1], max_n y, argmax_n y (as double), min_n y, max_n |dydt| (0.0 when dydt is NULL) }.
+ * Comparisons are plain > and <: a NaN entry never wins, ties resolve to the lowest node index.  The kernels are a
+ * translation unit of their own (csrc/monitor_kernels.inc), independent of any mechanism: compile
+ * rmt_n2_monitor_source() with rmt_n2_compile, load it with rmt_n2_monitor_create on the current device.  The object is
+ * independent of rmt_n2_handle.  rmt_n2_monitor_reduce enqueues ONE kernel on `hip_stream` and does not synchronise;
+ * y / dydt are DEVICE [E][V][N] reals (float when fp32), out DEVICE [E][V][5] doubles. */
+const char* rmt_n2_monitor_source(void);
+typedef struct rmt_n2_monitor rmt_n2_monitor;
+int rmt_n2_monitor_create(const void* code, size_t size, rmt_n2_monitor** out);
+void rmt_n2_monitor_destroy(rmt_n2_monitor* m);
+int rmt_n2_monitor_reduce(rmt_n2_monitor* m, void* hip_stream, const void* y, const void* dydt_or_null,
+                          int E, int V, int N, int fp32, double* out);
+/* how the last reduce was laid out: rows per workgroup - 4 = one wave per row (short rows, or rows enough to fill the
+ * device with waves), 1 = one workgroup per row (a few long rows); 0 before any */
+int rmt_n2_monitor_last_rows_per_block(const rmt_n2_monitor* m);
+
 const char* rmt_n2_last_error(void);
 int rmt_n2_abi_version(void);
 

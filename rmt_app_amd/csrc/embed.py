@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Concatenate the device template's parts (kernels/ORDER) and wrap the text into a C++ raw string
-literal (n2_kernels_embed.h) for rmt_n2.cpp.  `embed.py --cat` prints the template itself."""
+literal (n2_kernels_embed.h) for rmt_n2.cpp.  `embed.py --cat` prints the template itself;
+`embed.py --file SOURCE OUT` wraps one file the same way (the monitor's translation unit)."""
 import os
 import sys
 
@@ -21,10 +22,13 @@ def template():
 
 
 if __name__ == "__main__":
-    text = template()
-    if sys.argv[1] == "--cat":
+    if sys.argv[1] == "--file":
+        text, out = open(os.path.join(HERE, sys.argv[2])).read(), sys.argv[3]
+    else:
+        text, out = template(), sys.argv[1]
+    if out == "--cat":
         sys.stdout.write(text)
     else:
         assert ')RMTSRC"' not in text
-        with open(sys.argv[1], "w") as f:
+        with open(out, "w") as f:
             f.write('R"RMTSRC(' + text + ')RMTSRC"\n')

@@ -18,6 +18,10 @@
 static const char* const k_template =
 #include "n2_kernels_embed.h"
     ;
+// the monitor's translation unit (monitor_kernels.inc): mechanism-independent, compiled on its own
+static const char* const k_monitor_source =
+#include "monitor_kernels_embed.h"
+    ;
 
 static thread_local std::string g_err;
 
@@ -88,13 +92,14 @@ struct DeviceGuard {
     int prev = -1;
     bool switched = false;
     hipError_t err = hipSuccess;
-    explicit DeviceGuard(const rmt_n2_handle* h) {
+    explicit DeviceGuard(int device) {
         err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != h->device) {
-            err = hipSetDevice(h->device);
+        if (err == hipSuccess && prev != device) {
+            err = hipSetDevice(device);
             switched = err == hipSuccess;
         }
     }
+    explicit DeviceGuard(const rmt_n2_handle* h) : DeviceGuard(h->device) {}
     ~DeviceGuard() {
         if (switched) (void)hipSetDevice(prev);
     }
@@ -694,3 +699,93 @@ extern "C" int rmt_n2_status(rmt_n2_handle* h, uint32_t* flags_host) {
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------- monitor
+// Row reductions of a state in device memory (monitor_kernels.inc).  Independent of rmt_n2_handle: the code object is
+// mechanism-independent, the sizes are run-time arguments.
+// Layout of a reduce (measured on MI355X, profiles/monitor.md), 256 threads per workgroup:
+//  * one WAVE per row (four rows per workgroup) for rows of at most RMT_N2_MONITOR_WAVE_BYTES, and for longer rows when
+//    there are at least RMT_N2_MONITOR_ROWS_PER_CU rows per CU, one per SIMD: the waves alone fill the device
+//    (2048 x 7 rows of 8 KiB: 19.7 us = 5.9 TB/s against 39 us with a workgroup per row);
+//  * else one WORKGROUP per row (a few long rows; ONE 7 x 16384-node reactor: 6.3 us against 12.3 us by waves).
+// The environment variables RMT_N2_MONITOR_WAVE_BYTES (rows up to this size by a wave, all others by a workgroup) and
+// RMT_N2_MONITOR_BLOCK (threads of the workgroup-per-row form, up to 1024; 512 and 1024 measured slower as soon as there
+// are more rows than CUs) replace the rule for measurements.
+#define RMT_N2_MONITOR_BLOCK 256
+#define RMT_N2_MONITOR_WGS_PER_CU 8       // grid cap: the rows beyond it are walked grid-stride
+#define RMT_N2_MONITOR_WAVE_BYTES 8192
+#define RMT_N2_MONITOR_ROWS_PER_CU 4
+
+struct rmt_n2_monitor {
+    int device = 0, n_cus = 0, last_rows_per_block = 0;
+    hipModule_t module = nullptr;
+    hipFunction_t f64 = nullptr, f32 = nullptr;
+};
+
+extern "C" const char* rmt_n2_monitor_source(void) { return k_monitor_source; }
+
+extern "C" void rmt_n2_monitor_destroy(rmt_n2_monitor* m) {
+    if (!m) return;
+    DeviceGuard guard_(m->device);
+    if (m->module) (void)hipModuleUnload(m->module);
+    delete m;
+}
+
+extern "C" int rmt_n2_monitor_create(const void* code, size_t size, rmt_n2_monitor** out) {
+    if (!code || !size || !out) return fail("rmt_n2_monitor_create: null argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail("no HIP device available: the monitor has no CPU fallback");
+    rmt_n2_monitor* m = new rmt_n2_monitor();
+    hipError_t e = hipGetDevice(&m->device);
+    if (e == hipSuccess) e = hipModuleLoadData(&m->module, code);
+    if (e == hipSuccess) e = hipModuleGetFunction(&m->f64, m->module, "rmt_n2_monitor_rows_f64");
+    if (e == hipSuccess) e = hipModuleGetFunction(&m->f32, m->module, "rmt_n2_monitor_rows_f32");
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&m->n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
+    if (e != hipSuccess) {
+        fail("rmt_n2_monitor_create: %s", hipGetErrorString(e));
+        rmt_n2_monitor_destroy(m);
+        return 1;
+    }
+    *out = m;
+    return 0;
+}
+
+extern "C" int rmt_n2_monitor_reduce(rmt_n2_monitor* m, void* hip_stream, const void* y, const void* dydt_or_null,
+                                     int E, int V, int N, int fp32, double* out) {
+    if (!m || !y || !out) return fail("rmt_n2_monitor_reduce: null argument");
+    if (E < 1 || V < 1 || N < 1) return fail("rmt_n2_monitor_reduce: bad sizes E=%d V=%d N=%d", E, V, N);
+    const size_t real_size = fp32 ? 4 : 8;
+    if (((size_t)y % real_size) || ((size_t)dydt_or_null % real_size) || ((size_t)out % sizeof(double)))
+        return fail("rmt_n2_monitor_reduce: misaligned pointer");
+    DeviceGuard guard_(m->device);
+    if (guard_.err != hipSuccess)
+        return fail("cannot switch to device %d of this monitor: %s", m->device, hipGetErrorString(guard_.err));
+    static const long long env_wave_bytes = [] {  // tuning overrides, read once
+        const char* v = getenv("RMT_N2_MONITOR_WAVE_BYTES");
+        return v ? atoll(v) : -1LL;
+    }();
+    static const int env_block = [] {
+        const char* v = getenv("RMT_N2_MONITOR_BLOCK");
+        const int n = v ? atoi(v) : 0;
+        return n >= 64 && n <= 1024 && n % 64 == 0 ? n : 0;
+    }();
+    long long rows = (long long)E * V;
+    const long long row_bytes = (long long)N * (long long)real_size;
+    const bool per_wave = env_wave_bytes >= 0 ? row_bytes <= env_wave_bytes
+                                              : (row_bytes <= RMT_N2_MONITOR_WAVE_BYTES ||
+                                                 rows >= (long long)m->n_cus * RMT_N2_MONITOR_ROWS_PER_CU);
+    const int block = !per_wave && env_block ? env_block : RMT_N2_MONITOR_BLOCK;
+    int rows_per_block = per_wave ? block / 64 : 1;
+    long long grid = (rows + rows_per_block - 1) / rows_per_block;
+    const long long cap = (long long)m->n_cus * RMT_N2_MONITOR_WGS_PER_CU;
+    if (grid > cap) grid = cap;
+    void* args[] = {(void*)&y, (void*)&dydt_or_null, (void*)&out, (void*)&rows, (void*)&N, (void*)&rows_per_block};
+    HIP_OK(hipModuleLaunchKernel(fp32 ? m->f32 : m->f64, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, 0,
+                                 (hipStream_t)hip_stream, args, nullptr));
+    m->last_rows_per_block = rows_per_block;
+    return 0;
+}
+
+extern "C" int rmt_n2_monitor_last_rows_per_block(const rmt_n2_monitor* m) { return m ? m->last_rows_per_block : 0; }

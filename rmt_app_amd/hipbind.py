@@ -15,6 +15,12 @@ CACHE_DIR = os.path.join(_HERE, "_kcache")
 ABI_VERSION = 2
 
 
+def monitor_rows_per_block(E, V, N, real_size, n_cus):
+    """Rows per workgroup rmt_n2_monitor_reduce launches with (csrc/rmt_n2.cpp RMT_N2_MONITOR_*): 4 = one wave per row, for
+    rows of at most 8 KiB or when there are at least 4 rows per CU; else 1 = one workgroup per row."""
+    return 4 if int(N)*int(real_size) <= 8192 or int(E)*int(V) >= 4*int(n_cus) else 1
+
+
 class RmtN2Error(RuntimeError):
     pass
 
@@ -69,6 +75,12 @@ def lib():
     L.rmt_n2_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rmt_n2_last_geometry.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.rmt_n2_fallbacks.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rmt_n2_monitor_source.restype = cp
+    L.rmt_n2_monitor_create.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.rmt_n2_monitor_destroy.argtypes = [vp]
+    L.rmt_n2_monitor_destroy.restype = None
+    L.rmt_n2_monitor_reduce.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.rmt_n2_monitor_last_rows_per_block.argtypes = [vp]
     L.rmt_n2_hiprtc_path.restype = cp
     L.rmt_n2_compile_options.restype = cp
     if L.rmt_n2_abi_version() != ABI_VERSION:
@@ -84,6 +96,51 @@ def check(rc):
 
 def kernel_template():
     return lib().rmt_n2_kernel_template().decode()
+
+
+def monitor_source():
+    """The monitor's translation unit (csrc/monitor_kernels.inc, embedded in the library next to the template)."""
+    return lib().rmt_n2_monitor_source().decode()
+
+
+def monitor_code(arch="gfx950"):
+    """Code object of the monitor kernels from the in-tree cache (compiled on first use; works without a GPU)."""
+    import hashlib
+    src = monitor_source()
+    return compile_cached(src, "monitor-" + hashlib.sha256(src.encode()).hexdigest()[:24], arch)
+
+
+class Monitor:
+    """rmt_n2_monitor on the current device: row reductions of a state tensor [E][V][N] into out [E][V][5] doubles
+    = {y[N-1], max, argmax, min, max|dydt|} (include/rmt_n2.h).  Independent of any mechanism."""
+
+    def __init__(self, arch="gfx950", code=None):
+        code = monitor_code(arch) if code is None else code
+        self._code = C.create_string_buffer(code, len(code))
+        m = C.c_void_p()
+        check(lib().rmt_n2_monitor_create(C.cast(self._code, C.c_void_p), len(code), C.byref(m)))
+        self.m = m
+
+    def reduce(self, stream, y_ptr, dydt_ptr, E, V, N, fp32, out_ptr):
+        """Enqueue the reduction on `stream` (a hipStream_t as integer); nothing is synchronised."""
+        check(lib().rmt_n2_monitor_reduce(self.m, C.c_void_p(stream), C.c_void_p(y_ptr),
+                                          C.c_void_p(dydt_ptr) if dydt_ptr else None, int(E), int(V), int(N),
+                                          int(bool(fp32)), C.c_void_p(out_ptr)))
+
+    def last_rows_per_block(self):
+        """4: the last reduce ran one wave per row, 1: one workgroup per row."""
+        return int(lib().rmt_n2_monitor_last_rows_per_block(self.m))
+
+    def close(self):
+        if getattr(self, "m", None):
+            lib().rmt_n2_monitor_destroy(self.m)
+            self.m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def compile_source(source, arch="gfx950", extra_opts=""):

@@ -15,8 +15,8 @@ from timeit import default_timer as timer
 
 import numpy as np
 
-from . import plan
-from .n2 import (ROUND_FUN_ACCURACY, integrate_intervals, mechanism_for, open_auto, open_members, resolve_ivp,
+from . import monitor, plan
+from .n2 import (PIPELINE_BYTES, ROUND_FUN_ACCURACY, attach_monitor, integrate_intervals, mechanism_for, open_auto, open_members, resolve_ivp,
                  rk45_geometry, ros4_block)
 from .settings import solverSetting
 
@@ -57,6 +57,9 @@ def run_m2(modelInput, members_inputs=None):
     from .ensemble import active_ranks, guarded
     sync = active_ranks(len(inputs)) if members_inputs else None       # one rank of a torchrun job?
     block, npt = cfg.get('block'), cfg.get('nodes-per-thread')
+    mon = monitor.parse(modelInput, tNo)             # "monitor": time series between the output times (monitor.py)
+    if mon is not None:
+        mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
     if ivp == "hip-ros4" and block is None:
         block, npt = ros4_block(mech.V, zNo, quad=False), 1
     defines = {}
@@ -82,7 +85,9 @@ def run_m2(modelInput, members_inputs=None):
                 for e in range(n_pack):
                     packs[e].append(pack_interval(Yg[e], mech, zNo, t1))
         stats = integrate_intervals(dev, y, cfg, ivp, opTSpan, len(named_local), zNo, quiet or not packer,
-                                    on_interval, sync)
+                                    on_interval, sync, mon=mon)
+        monitors = attach_monitor(stats, mon, sync, lambda e, raw: monitor.result_entry(
+            raw, mon.times, mech, zNo, None, "M2", inputs[e]['reactor']['ReLe'], mon.residual))
     finally:
         dev.close()
     ReLe = modelInput['reactor']['ReLe']
@@ -93,6 +98,11 @@ def run_m2(modelInput, members_inputs=None):
     if members_inputs:
         res["ensemble"] = [dict(result_lists(p, mi['reactor']['ReLe'], zNo, opTSpan), dataPack=p)
                            for p, mi in zip(packs, inputs)] if packer else None
+    if monitors:
+        res["monitor"] = monitors[0]
+        if members_inputs:
+            for entry, m in zip(res["ensemble"], monitors):
+                entry["monitor"] = m
     if sync is not None:
         res["ensemble-shard"] = {"rank": sync.rank, "world": sync.world, "members": [sync.lo, sync.hi]}
     return res

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import hipbind, plan, schedule
+from . import hipbind, monitor, plan, schedule
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
 
@@ -362,6 +362,7 @@ class N2Device:
     def use_current_stream(self):
         s = self.torch.cuda.current_stream(self.device).cuda_stream
         hipbind.check(hipbind.lib().rmt_n2_set_stream(self.h, C.c_void_p(s)))
+        self._stream = s
 
     def set_members(self, members):
         """Replace the per-reactor constant rows (same E) without recompiling - e.g. the next
@@ -391,6 +392,9 @@ class N2Device:
         hipbind.check(hipbind.lib().rmt_n2_set_mode(self.h, {"auto": 0, "reg": 1, "mem": 2, "chain": 3}[mode]))
 
     def close(self):
+        if getattr(self, "_mon", None) is not None:
+            self._mon.close()
+            self._mon = None
         if getattr(self, "h", None):
             hipbind.lib().rmt_n2_destroy(self.h)
             self.h = None
@@ -400,6 +404,23 @@ class N2Device:
             self.close()
         except Exception:
             pass
+
+    def monitor(self, y, out, residual=False):
+        """Queue the row reductions of the state y on the device's stream: out (device double [E][V][5]) = per member
+        and variable {y[N-1], max, argmax, min, max|dy/dt|} - the last one only with ``residual`` (rmt_n2_rhs at y is
+        queued first), else 0.  Nothing is copied or synchronised.  The monitor object (mechanism-independent kernels,
+        csrc/monitor_kernels.inc) is created on first use."""
+        self._chk_state(y)
+        assert out.is_cuda and out.dtype == self.torch.float64 and out.is_contiguous()
+        assert out.numel() == self.E*self.mech.V*monitor.SLOTS, "monitor output must be [E][V][5] doubles"
+        if getattr(self, "_mon", None) is None:
+            arch = self.torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]
+            with self.torch.cuda.device(self.device):
+                self._mon = hipbind.Monitor(arch)
+        dydt = self.rhs(y) if residual else None       # (stays allocated until the stream is past the reduce: torch's
+        #                                                 caching allocator hands memory out in stream order)
+        self._mon.reduce(self._stream, y.data_ptr(), dydt.data_ptr() if residual else 0, self.E, self.mech.V, self.N,
+                         self.fp32, out.data_ptr())
 
     def to_device(self, y):
         t = self.torch.as_tensor(np.ascontiguousarray(y), dtype=self.dtype)
@@ -566,6 +587,9 @@ class AutoStepper:
 
     def rk45_stats(self):
         return self.last.rk45_stats()
+
+    def monitor(self, y, out, residual=False):
+        self.last.monitor(y, out, residual)
 
     def raise_on_flags(self):
         self.last.raise_on_flags()
@@ -921,19 +945,35 @@ PIPELINE_BYTES = 1 << 30       # pinned host memory one batch of queued output i
 
 
 def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_interval, sync=None, outlet=False,
-                        forcing=None):
+                        forcing=None, mon=None):
     """The reference's time loop (pbHomoReactor.py:3589-3690, pbReactor.py:711-762): one device
     launch per output interval; ``on_interval(i, t1, Y_host)`` packs the end state ([E][V*zNo], or [E][V] = the
     outlet node with ``outlet``).  With ``sync`` (multi-rank ensemble) a failure on any rank is raised on every
     rank before the next gather.
     ``forcing`` (solver-config "schedule"): the walk goes over output times AND breakpoints (Forcing.launches; only a
-    launch that ends at an output time is packed), and the device rows are refreshed before each launch is queued."""
+    launch that ends at an output time is packed), and the device rows are refreshed before each launch is queued.
+    ``mon`` (a monitor.Monitor, solver-config "monitor"): the walk is split at the sample times as well; behind a launch
+    that ends at sample k the row reductions of the state are queued into slice k of ONE device buffer [K][E][V][5]
+    (sample 0 before the first launch; with "residual" behind rmt_n2_rhs at that state).  Nothing is copied or
+    synchronised per sample: the buffer comes back once, at the end, as ``stats["monitor-raw"]`` ([K][E_local][V][5];
+    the callers pop it).  A run that raises on flags returns no monitor."""
     tNo = len(opTSpan) - 1
-    # (t0, t1, index of the output time the launch ends at or None)
+    # (t0, t1, index of the output time the launch ends at or None, index of the sample it ends at or None)
     launches = forcing.launches if forcing is not None else \
         [(float(opTSpan[i]), float(opTSpan[i + 1]), i + 1) for i in range(tNo)]
+    launches = mon.refine(launches, float(opTSpan[-1])) if mon is not None else [l + (None,) for l in launches]
     nL = len(launches)
+    mbuf = None
+    if mon is not None:
+        import torch
+        mbuf = torch.zeros((mon.K, y.shape[0], y.shape[1]//zNo, monitor.SLOTS), dtype=torch.float64, device=y.device)
+
+    def sample(k):
+        if mbuf is not None and k is not None:
+            dev.monitor(y, mbuf[k], mon.residual)
     stats = {"steps": 0, "rhs_evals": 0, "node_steps": 0, "accepted": None, "rejected": None}
+    if mon is not None:
+        stats["launches"] = nL
     _progress(0, tNo + 1, quiet)
     def launch(i, t0, t1):
         if ivp == "hip-rk4":
@@ -980,15 +1020,17 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
         per = E_loc*(y.shape[1]//zNo if outlet else y.shape[1])*y.element_size()
         batch = int(max(1, min(nL, PIPELINE_BYTES//max(per, 1))))
         check = False
+        sample(0)
         for lo in range(0, nL, batch):
             hi = min(nL, lo + batch)
             hosts, counters, landed, staged = [], [], [], []
             for i in range(lo, hi):
-                t0, t1, kout = launches[i]
+                t0, t1, kout, ksample = launches[i]
                 _progress(i + 1, nL + 1, quiet)
                 if forcing is not None:                          # (the page-locked rows stay alive until the batch has landed)
                     staged.append(forcing.refresh(dev, t0, t1, queued=True))
                 launch(i, t0, t1)
+                sample(ksample)                                  # queued right behind its launch, into slice ksample
                 host = None
                 if kout is not None:
                     src = y.reshape(E_loc, -1, zNo)[:, :, zNo - 1] if outlet else y
@@ -1013,21 +1055,34 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
                     on_interval(launches[i][2] - 1, float(opTSpan[launches[i][2]]), hosts[k].numpy().astype(np.float64))
             dev.raise_on_flags()                                  # (sticky status words: whatever a launch of the batch flagged)
             del staged
+        if mbuf is not None:
+            stats["monitor-raw"] = mbuf.cpu().numpy()             # the ONE copy of the monitor buffer
         return finish_stats(stats, ivp, n_members, nL, zNo, dev.jacobian_evals)
 
+    if sync is None:
+        sample(0)
+    else:
+        err = None
+        try:
+            sample(0)
+        except Exception as e:                  # noqa: BLE001 - re-raised on every rank by agree()
+            err = e
+        sync.agree(err)
     for i in range(nL):
-        t0, t1, kout = launches[i]
+        t0, t1, kout, ksample = launches[i]
         _progress(i + 1, nL + 1, quiet)
         if sync is None:
             if forcing is not None:
                 forcing.refresh(dev, t0, t1)
             launch(i, t0, t1)
+            sample(ksample)
         else:                                   # whatever goes wrong on one rank is raised on every rank
             err = None
             try:
                 if forcing is not None:
                     forcing.refresh(dev, t0, t1)
                 launch(i, t0, t1)
+                sample(ksample)
             except Exception as e:              # noqa: BLE001 - re-raised on every rank by agree()
                 err = e
             sync.agree(err)
@@ -1047,6 +1102,8 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
         on_interval(i, t1, Yh)
     if ivp == "hip-auto":
         stats["method-per-interval"] = list(dev.choices)
+    if mbuf is not None:
+        stats["monitor-raw"] = mbuf.cpu().numpy()                 # the ONE copy of the monitor buffer
     if sync is not None:
         stats = gather_stats(stats, sync, ivp, nL, zNo, dev.jacobian_evals)
     else:
@@ -1054,6 +1111,21 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     if ivp == "hip-auto":
         stats["rhs_evals"] = dev.rhs_evals          # includes the probe and any abandoned explicit attempt
     return stats
+
+
+def attach_monitor(stats, mon, sync, convert):
+    """The monitor entries of every member, on the process that returns the results: the raw buffer integrate_intervals
+    left in ``stats`` ([K][E_local][V][5]; removed from the record), gathered to rank 0 ONCE in a multi-rank job, each
+    member converted by ``convert(e, raw [K][V][5])``.  None without a monitor and on the other ranks."""
+    raw = stats.pop("monitor-raw", None)
+    if mon is None or raw is None:
+        return None
+    raw = np.ascontiguousarray(np.swapaxes(raw, 0, 1))            # [E_local][K][V][5]
+    if sync is not None:
+        raw = sync.gather(raw)
+        if raw is None:
+            return None
+    return [convert(e, raw[e]) for e in range(raw.shape[0])]
 
 
 def run_n2(modelInput, members_inputs=None):
@@ -1078,6 +1150,10 @@ def run_n2(modelInput, members_inputs=None):
     block, npt = cfg.get('block'), cfg.get('nodes-per-thread')
     # "schedule": time-varying inlet / coolant conditions (schedule.py); absent = None = exactly the run without it
     sched = schedule.parse(modelInput, members_inputs, ivp)
+    # "monitor": time series between the output times (monitor.py); absent = None = exactly the run without it
+    mon = monitor.parse(modelInput, tNo)
+    if mon is not None:
+        mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
     forcing = None
     if sched is not None:
         if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
@@ -1127,12 +1203,14 @@ def run_n2(modelInput, members_inputs=None):
                     for e, pk in enumerate(pack_intervals(Yg, named, mech, 1 if outlet else zNo, t1, modelId)):
                         packs[e].append(pk)
         stats = integrate_intervals(dev, y, cfg, ivp, np.linspace(0, opT, tNo + 1), len(named_local),
-                                    zNo, quiet or not packer, on_interval, sync, outlet, forcing)
+                                    zNo, quiet or not packer, on_interval, sync, outlet, forcing, mon)
+        monitors = attach_monitor(stats, mon, sync, lambda e, raw: monitor.result_entry(
+            raw, mon.times, mech, zNo, named[e], "N2", residual=mon.residual))
         if forcing is not None:
             # which kernel forms ran: "reg" = the on-chip steppers, "mem" = the memory-resident ones; and what
             # rmt_n2_last_geometry reports for the last launch (workgroups per reactor, teams)
             stats["device-mode"] = dict(forcing.modes)
-            stats["launches"] = len(forcing.launches)
+            stats.setdefault("launches", len(forcing.launches))       # (a monitored run: its refined list's)
             last = getattr(dev, "last", dev)
             if hasattr(last, "last_geometry"):
                 stats["last-geometry"] = last.last_geometry()
@@ -1145,6 +1223,11 @@ def run_n2(modelInput, members_inputs=None):
     if members_inputs:
         # multi-rank: rank 0 holds the whole sweep, the other ranks None (and an empty dataPack)
         resPack["ensemble"] = [{"dataPack": p} for p in packs] if packer else None
+    if monitors:
+        resPack["monitor"] = monitors[0]
+        if members_inputs:
+            for entry, m in zip(resPack["ensemble"], monitors):
+                entry["monitor"] = m
     if sync is not None:
         resPack["ensemble-shard"] = {"rank": sync.rank, "world": sync.world, "members": [sync.lo, sync.hi]}
     if displayResult and packer:

@@ -30,6 +30,8 @@ def rmtExe(modelInput):
         if modelType != "N2" and modelInput['solver-config'].get('schedule') is not None:
             raise ValueError("solver-config 'schedule' (time-varying inlet / coolant conditions) is only available for "
                              "model 'N2' (got model %r)" % (modelType,))
+        from .monitor import check_model
+        check_model(modelInput)               # solver-config 'monitor': models N2 and M2 only
         if modelType == "N2":
             from .n2 import run_n2
             ensemble = modelInput['solver-config'].get('ensemble')

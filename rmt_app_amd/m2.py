@@ -11,14 +11,10 @@ The reference returns only plot lists from runM2 (pbReactor.py:835-840: the temp
 of every output time); ``run_m2`` returns exactly those two keys plus ``dataPack`` (the per-interval
 records the reference builds internally, :745-753), ``computation-time`` and ``device-stats``.
 """
-from timeit import default_timer as timer
-
 import numpy as np
 
-from . import monitor, plan
-from .n2 import (PIPELINE_BYTES, ROUND_FUN_ACCURACY, attach_monitor, integrate_intervals, mechanism_for, open_auto, open_members, resolve_ivp,
-                 rk45_geometry, ros4_block)
-from .settings import solverSetting
+from . import plan
+from .n2 import run_dynamic
 
 
 def pack_interval(Yflat, mech, zNo, t_end):
@@ -43,66 +39,9 @@ def result_lists(packs, ReLe, zNo, opTSpan):
 
 
 def run_m2(modelInput, members_inputs=None):
-    start = timer()
-    cfg = modelInput['solver-config']
-    ivp = resolve_ivp(cfg['ivp'])
-    zNo = int(cfg.get('zNo', solverSetting['S2']['zNo']))           # pbReactor.py:625
-    tNo = int(cfg.get('tNo', solverSetting['S2']['tNo']))           # :694
-    quiet = bool(cfg.get('quiet', False))
-    if cfg.get('dtype', 'fp64') not in ('fp64', 'float64'):
+    if modelInput['solver-config'].get('dtype', 'fp64') not in ('fp64', 'float64'):
         raise ValueError("model M2 is built in fp64 only")
-    opT = modelInput['operating-conditions']['period']
-    inputs = list(members_inputs) if members_inputs else [modelInput]
-    mech = mechanism_for(modelInput, inputs, cfg)
-    from .ensemble import active_ranks, guarded
-    sync = active_ranks(len(inputs)) if members_inputs else None       # one rank of a torchrun job?
-    block, npt = cfg.get('block'), cfg.get('nodes-per-thread')
-    mon = monitor.parse(modelInput, tNo)             # "monitor": time series between the output times (monitor.py)
-    if mon is not None:
-        mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
-    if ivp == "hip-ros4" and block is None:
-        block, npt = ros4_block(mech.V, zNo, quad=False), 1
-    defines = {}
-    if ivp == "hip-rk45" and block is None:
-        block, npt, defines = rk45_geometry(mech.V, zNo, E=len(inputs) if sync is None else max(sync.counts))
-    if ivp == "hip-auto":               # the reference's LSODA: automatic stiff / non-stiff choice (n2.AutoStepper)
-        dev, named_local, IV = open_auto(mech, inputs, zNo, plan.member_constants_m2, plan.initial_state_m2, sync,
-                                         False, None, block, npt)
-    else:
-        dev, named_local, IV = open_members(mech, inputs, zNo, plan.member_constants_m2, plan.initial_state_m2, sync,
-                                            block=block, npt=npt, defines=defines,
-                                            features=("ros4",) if ivp == "hip-ros4" else ())
-    packer = sync is None or sync.rank == 0          # rank 0 (or the only process) packs every member
-    n_pack = len(inputs) if packer else 0
-    opTSpan = np.linspace(0, opT, tNo + 1)                          # :695
-    try:
-        y = guarded(sync, dev.to_device, IV)
-        packs = [[] for _ in range(n_pack)]
-
-        def on_interval(i, t1, Yh):
-            Yg = Yh if sync is None else sync.gather(Yh)
-            if Yg is not None:
-                for e in range(n_pack):
-                    packs[e].append(pack_interval(Yg[e], mech, zNo, t1))
-        stats = integrate_intervals(dev, y, cfg, ivp, opTSpan, len(named_local), zNo, quiet or not packer,
-                                    on_interval, sync, mon=mon)
-        monitors = attach_monitor(stats, mon, sync, lambda e, raw: monitor.result_entry(
-            raw, mon.times, mech, zNo, None, "M2", inputs[e]['reactor']['ReLe'], mon.residual))
-    finally:
-        dev.close()
-    ReLe = modelInput['reactor']['ReLe']
-    res = result_lists(packs[0] if packs else [], ReLe, zNo, opTSpan)
-    res["dataPack"] = packs[0] if packs else []
-    res["computation-time"] = np.round(timer() - start, ROUND_FUN_ACCURACY)
-    res["device-stats"] = stats
-    if members_inputs:
-        res["ensemble"] = [dict(result_lists(p, mi['reactor']['ReLe'], zNo, opTSpan), dataPack=p)
-                           for p, mi in zip(packs, inputs)] if packer else None
-    if monitors:
-        res["monitor"] = monitors[0]
-        if members_inputs:
-            for entry, m in zip(res["ensemble"], monitors):
-                entry["monitor"] = m
-    if sync is not None:
-        res["ensemble-shard"] = {"rank": sync.rank, "world": sync.world, "members": [sync.lo, sync.hi]}
-    return res
+    return run_dynamic(modelInput, members_inputs, "M2", plan.member_constants_m2, plan.initial_state_m2,
+                       lambda Yg, named, mech, zNo, t1: [pack_interval(Y, mech, zNo, t1) for Y in Yg],
+                       lambda dataPack, mi, zNo, opTSpan: dict(result_lists(dataPack, mi['reactor']['ReLe'], zNo, opTSpan),
+                                                               dataPack=dataPack))

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import plan
 from . import n2 as _n2
-from .settings import DEVICE_DEFAULTS, MODEL_SETTING, ROUND_FUN_ACCURACY, solverSetting
+from .settings import MODEL_SETTING, ROUND_FUN_ACCURACY, solverSetting
 
 
 def pack_profile(U, named, mech, modelId, elapsed):
@@ -51,44 +51,17 @@ def run_n1(modelInput, members_inputs=None):
     displayResult = cfg['display-result'] == "True"
     zNo = int(cfg.get('zNo', solverSetting['N1']['zNo']))
     nout = zNo + 1
-    all_inputs = list(members_inputs) if members_inputs else [modelInput]
-    mech = _n2.mechanism_for(modelInput, all_inputs, cfg)
-    # as one rank of a torch.distributed job: integrate this rank's contiguous block of profiles.  Every
-    # rank-local phase (packing, device creation, the launch + status read) runs under ensemble.guarded: a failure
-    # on one rank is raised on every rank before the next collective.
-    from .ensemble import active_ranks, guarded
-    sync = active_ranks(len(all_inputs)) if members_inputs else None
-    inputs = all_inputs if sync is None else all_inputs[sync.lo:sync.hi]
-
-    def pack_and_open():
-        pairs = [plan.member_constants_n1(mi, mech) for mi in inputs]
-        rows1 = np.ascontiguousarray(np.array([r for _, r in pairs]))
-        # the handle is an N2 handle (same generated module); its N2 member rows are not used here
-        dummy = np.array([plan.member_constants(mi, mech, 64)[1] for mi in inputs])
-        # MODEL_SETTING['GaMaCoTe0'] != "MAX": model N1 runs with per-species scaling in the reference (:2819, 3159)
-        defs = {"RMT_N1_SCALE_FIX": "1"} if MODEL_SETTING['GaMaCoTe0'] != "MAX" else None
-        return pairs, rows1, _n2.device_cls()(mech, dummy, 64, block=64, npt=1, specialize=False, features=("n1",),
-                                              defines=defs)
-    pairs, rows1, dev = guarded(sync, pack_and_open)
-    try:
-        def launch():
-            out = dev.n1_profile(rows1, nout, float(cfg.get('rtol', DEVICE_DEFAULTS['n1-rtol'])),
-                                 float(cfg.get('atol', DEVICE_DEFAULTS['n1-atol'])), float(cfg.get('h0', 1e-6)),
-                                 int(cfg.get('max-steps', 10**7)))
-            dev.raise_on_flags()
-            return dev.rk45_stats(), out
-        stats, U = guarded(sync, launch)
-    finally:
-        dev.close()
-    if sync is not None:                    # rank 0 returns every member's profile, the other ranks None
-        U = sync.gather(U)
-        stats = {k: sync.gather(stats[k]) for k in ("accepted", "rejected")}
-        if U is None:
-            return None
-        inputs = all_inputs
-        pairs = [plan.member_constants_n1(mi, mech) for mi in inputs]
+    # the handle is an N2 handle (same generated module); its N2 member rows are not used here.
+    # MODEL_SETTING['GaMaCoTe0'] != "MAX": model N1 runs with per-species scaling in the reference (:2819, 3159)
+    got = _n2.steady_profiles(
+        modelInput, members_inputs, plan.member_constants_n1, nout,
+        {"RMT_N1_SCALE_FIX": "1"} if MODEL_SETTING['GaMaCoTe0'] != "MAX" else None,
+        handle_rows=lambda inputs, mech: np.array([plan.member_constants(mi, mech, 64)[1] for mi in inputs]))
+    if got is None:
+        return None
+    mech, named, U, stats = got
     elapsed = np.round(timer() - start, ROUND_FUN_ACCURACY)
-    packs = [pack_profile(U[e], pairs[e][0], mech, modelInput['model'], elapsed) for e in range(len(inputs))]
+    packs = [pack_profile(U[e], named[e], mech, modelInput['model'], elapsed) for e in range(len(named))]
     for p, acc, rej in zip(packs, stats["accepted"], stats["rejected"]):
         p["device-stats"] = {"accepted": int(acc), "rejected": int(rej)}
     if displayResult:

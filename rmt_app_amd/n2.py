@@ -7,6 +7,7 @@ The reference calls scipy's solve_ivp once per output interval with a Python RHS
 torch is used only as the owner of device memory and streams.
 """
 import ctypes as C
+from collections import namedtuple
 from timeit import default_timer as timer
 
 import os
@@ -14,6 +15,7 @@ import os
 import numpy as np
 
 from . import hipbind, monitor, plan, schedule
+from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
 
@@ -222,15 +224,24 @@ def kcache_choice(mech, N, fp32, block, npt, lds_state, defines):
     return defs, want
 
 
-def device_source(mech, members, N, fp32=False, block=None, npt=None, lds_state=None, defines=None,
-                  specialize=None, features=(), have_code=False):
-    """What N2Device compiles for (mechanism, member rows, mesh): geometry, the prelude #defines (optional
-    kernel families, model-M2 sweeps, sweep-invariant member fields as literals) and the translation unit.
-    Needs no GPU - `precompile` uses it to fill the in-tree code-object cache ahead of time."""
-    members = np.ascontiguousarray(members, dtype=np.float64)
-    if members.ndim == 1:
-        members = members.reshape(1, -1)
-    E = members.shape[0]
+CodePlan = namedtuple("CodePlan", "block npt lds_state defines features")
+
+
+def code_plan(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),
+              rows=None, specialize=None, literals=None, newton=True):
+    """WHICH code object a run loads - the one place that decides it: geometry (the caller's, else choose_geometry for E
+    members per GPU), the RK4 rate-constant cache (kcache_choice), the optional kernel families, the stiff stepper's
+    layout, model M2's Newton sweeps and the sweep-invariant member fields as literals.  The single-process route passes
+    its member ``rows`` (E and, with ``specialize``, the literals come from them; a single reactor is NOT specialised by
+    default - every new operating point would cost a 2-3 s JIT); a multi-rank job passes the members per GPU and the
+    defines its ranks agreed on (``literals``).  A forced code object takes no literal for a field its schedule moves.
+    The translation unit and its cache key (plan_unit) and the hipRTC options (compile_options) follow from the record;
+    needs no GPU."""
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        rows = rows.reshape(1, -1) if rows.ndim == 1 else rows
+        E = rows.shape[0] if E is None else E
+        specialize = E >= 2 if specialize is None else specialize
     b, n = choose_geometry(int(N), mech.V, fp32, E)
     block, npt = int(block or b), int(npt or n)
     defs, lds_state = kcache_choice(mech, N, fp32, block, npt, lds_state, defines)
@@ -239,16 +250,14 @@ def device_source(mech, members, N, fp32=False, block=None, npt=None, lds_state=
     for f in features:
         defs[FEATURE_DEFINES[f]] = "1"
     if "ros4" in features and "RMT_ROS_QUAD" not in defs and ros4_quad(mech, fp32) and npt == 1:
-        defs["RMT_ROS_QUAD"] = "1"            # wide mechanism: one node on four lanes (the C library is told below)
-    if getattr(mech, "model", "N2") == "M2" and "RMT_M2_NEWTON" not in defs and not have_code:
-        defs["RMT_M2_NEWTON"] = str(plan.m2_newton_sweeps(members, mech, int(N)))
-    # sweep-invariant member fields become literals (frees SGPRs); a single reactor is NOT
-    # specialised by default - every new operating point would cost a 2-3 s JIT
-    if specialize is None:
-        specialize = E >= 2
-    if specialize:
-        lit = plan.uniform_member_defines(members[:, :mech.row_width], mech.S)
-        defs.update(forced_literals(lit) if is_forced(defs) else lit)
+        defs["RMT_ROS_QUAD"] = "1"            # wide mechanism: one node on four lanes (N2Device tells the C library)
+    if getattr(mech, "model", "N2") == "M2" and "RMT_M2_NEWTON" not in defs and rows is not None and newton:
+        # (a multi-rank job passes the maximum over its ranks as a define)
+        defs["RMT_M2_NEWTON"] = str(plan.m2_newton_sweeps(rows, mech, int(N)))
+    if specialize:                            # sweep-invariant member fields become literals (frees SGPRs)
+        literals = plan.uniform_member_defines(rows[:, :mech.row_width], mech.S)
+    if literals:
+        defs.update(forced_literals(literals) if is_forced(defs) else literals)
     # "RMT_KCACHE": "1" (kcache_choice above, or the caller's own): the on-chip RK4 stepper caches the temperature-only
     # rate constants per node in LDS - that has to fit
     gen = plan.KCACHE_GEN[str(defs.get("RMT_KCACHE_GEN", "1"))]
@@ -265,11 +274,29 @@ def device_source(mech, members, N, fp32=False, block=None, npt=None, lds_state=
         raise ValueError("RMT_KCACHE=1: the cache of the temperature-only rate constants (%d doubles per node) does not "
                          "fit this geometry (needs the on-chip RK4 stepper with its vectors in registers, model N2, fp64)"
                          % mech.kcache_slots())
+    return CodePlan(block, npt, lds_state, defs, tuple(features))
+
+
+def plan_unit(mech, fp32, cp):
+    """(translation unit, cache key) of a CodePlan"""
     tpl = hipbind.kernel_template()
     # (the user's lds_state, possibly None, is what selects the per-kernel defaults)
-    src = mech.source(tpl, fp32, block, npt, lds_state, defs)
-    key = mech.digest(tpl, fp32, block, npt, lds_state, defs)
-    return block, npt, defs, src, key
+    return (mech.source(tpl, fp32, cp.block, cp.npt, cp.lds_state, cp.defines),
+            mech.digest(tpl, fp32, cp.block, cp.npt, cp.lds_state, cp.defines))
+
+
+def compile_plan(mech, fp32, cp, arch="gfx950", extra_opts=""):
+    """The code object of a CodePlan, from the in-tree cache or hipRTC (no GPU needed)."""
+    src, key = plan_unit(mech, fp32, cp)
+    return hipbind.compile_cached(src, key, arch, compile_options(cp.block, cp.npt, cp.features, extra_opts, cp.defines))
+
+
+def device_source(mech, members, N, fp32=False, block=None, npt=None, lds_state=None, defines=None,
+                  specialize=None, features=()):
+    """What N2Device compiles for (mechanism, member rows, mesh): (block, npt, prelude #defines, translation unit, cache
+    key)."""
+    cp = code_plan(mech, N, fp32, None, block, npt, lds_state, defines, features, members, specialize)
+    return (cp.block, cp.npt, cp.defines) + plan_unit(mech, fp32, cp)
 
 
 def compile_options(block, npt, features=(), extra_opts="", defines=None):
@@ -292,10 +319,50 @@ def compile_options(block, npt, features=(), extra_opts="", defines=None):
 def precompile(mech, members, N, arch="gfx950", extra_opts="", **kw):
     """Cross-compile (hipRTC, no GPU needed) the code object N2Device(mech, members, N, **kw) will load and
     leave it in the in-tree cache; returns its cache key."""
-    block, npt, _, src, key = device_source(mech, members, N, **kw)
-    hipbind.compile_cached(src, key, arch, compile_options(block, npt, kw.get("features", ()), extra_opts,
-                                                           kw.get("defines")))
-    return key
+    cp = code_plan(mech, N, rows=members, **kw)
+    compile_plan(mech, kw.get("fp32", False), cp, arch, extra_opts)
+    return plan_unit(mech, kw.get("fp32", False), cp)[1]
+
+
+def flag_error(flags):
+    """Device status words (one per reactor) -> the exception the reference's Python path raises inside the user lambdas
+    (SURVEY.md section 5 'Failure detection') for the first reactor that has one set; None when all are clear."""
+    bad = np.nonzero(flags)[0]
+    if len(bad) == 0:
+        return None
+    f = int(flags[bad[0]])
+    where = "reactor %d of %d (flags=0x%x)" % (bad[0], len(flags), f)
+    if f & FLAG_DOMAIN:
+        return ValueError("math domain error in " + where)
+    if f & FLAG_DIV0:
+        return ZeroDivisionError("float division by zero in " + where)
+    if f & FLAG_OVERFLOW:
+        return OverflowError("math range error in " + where)
+    if f & FLAG_STEP:
+        return RuntimeError("adaptive step control failed (step underflow / max steps) in " + where)
+    if f & FLAG_NONFINITE:
+        return FloatingPointError("state became NaN/Inf in " + where + " - step size too large?")
+    if f & FLAG_PRESSURE:
+        return RuntimeError("model M2: the Newton sweeps of the pressure march did not converge in "
+                            + where + " - pass defines={'RMT_M2_NEWTON': 4} (pressure drop > 15 % of P)")
+    return RuntimeError("device error in " + where)
+
+
+def stepper_args(cfg, stepper, first, auto=False):
+    """(rtol, atol, h0, max_steps) of N2Device.rk45 / .ros4 ("rk45" / "ros4") from the solver-config.  The first launch
+    of a stepper starts every reactor at h0; later ones RESUME (h0 < 0): each reactor starts from the step its own
+    controller proposed at the end of the previous launch (stats.h_last).  ``auto``: the explicit pair under "hip-auto"
+    has tolerances of its own."""
+    tol = "auto-rk45" if auto and stepper == "rk45" else stepper
+    h0 = float(cfg.get('h0', DEVICE_DEFAULTS[stepper + '-h0']))
+    return (float(cfg.get('rtol', DEVICE_DEFAULTS[tol + '-rtol'])), float(cfg.get('atol', DEVICE_DEFAULTS[tol + '-atol'])),
+            h0 if first else -h0, int(cfg.get('max-steps', DEVICE_DEFAULTS['rk45-max-steps'])))
+
+
+def step_counts(raw):
+    """(accepted, rejected) per reactor from the adaptive steppers' counters [E][4] = {t_end, h_last, accepted, rejected}
+    (the two counts travel as the bit patterns of int64)"""
+    return raw[:, 2].copy().view(np.int64), raw[:, 3].copy().view(np.int64)
 
 
 def _torch():
@@ -307,6 +374,9 @@ def _torch():
 
 class N2Device:
     """One compiled mechanism + E packed member rows on one GPU."""
+    # launches, row updates (set_members_async) and copies of the counters tensor (_stats) are queued on one stream, and
+    # nothing between two launches needs the host: integrate_intervals may queue several launches at once
+    stream_ordered = True
 
     def __init__(self, mech, members, N, fp32=False, block=None, npt=None, device=None,
                  extra_opts="", lds_state=None, defines=None, code=None, specialize=None,
@@ -323,16 +393,13 @@ class N2Device:
         self.E = members.shape[0]
         self.members = members
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self.features = tuple(features)
-        self.block, self.npt, self.defines, src, key = device_source(
-            mech, members, self.N, self.fp32, block, npt, lds_state, defines, specialize, self.features,
-            have_code=code is not None)
-        _, lds_state = kcache_choice(mech, self.N, self.fp32, self.block, self.npt, lds_state, defines)
-        self.lds_state = mech.lds_state(self.fp32, self.block, self.npt, lds_state)
-        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]
+        cp = code_plan(mech, self.N, self.fp32, None, block, npt, lds_state, defines, features, members, specialize,
+                       newton=code is None)
+        self.block, self.npt, self.defines, self.features = cp.block, cp.npt, cp.defines, cp.features
+        self.lds_state = mech.lds_state(self.fp32, self.block, self.npt, cp.lds_state)
         if code is None:      # an ensemble rank may receive rank 0's code object instead
-            code = hipbind.compile_cached(src, key, arch, compile_options(self.block, self.npt, self.features, extra_opts,
-                                                                          self.defines))
+            code = compile_plan(mech, self.fp32, cp, torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0],
+                                extra_opts)
         self._code = C.create_string_buffer(code, len(code))
         p = hipbind.Plan()
         p.abi_version = hipbind.ABI_VERSION
@@ -483,8 +550,8 @@ class N2Device:
 
     def rk45_stats(self):
         raw = self._stats.cpu().numpy()
-        return {"t_end": raw[:, 0].copy(), "h_last": raw[:, 1].copy(),
-                "accepted": raw[:, 2].copy().view(np.int64), "rejected": raw[:, 3].copy().view(np.int64)}
+        acc, rej = step_counts(raw)
+        return {"t_end": raw[:, 0].copy(), "h_last": raw[:, 1].copy(), "accepted": acc, "rejected": rej}
 
     def status(self):
         flags = np.zeros(self.E, dtype=np.uint32)
@@ -510,28 +577,9 @@ class N2Device:
         return ms.value
 
     def raise_on_flags(self):
-        """Turn device status words into the exception the reference's Python path raises inside
-        the user lambdas (SURVEY.md section 5 'Failure detection')."""
-        flags = self.status()
-        bad = np.nonzero(flags)[0]
-        if len(bad) == 0:
-            return
-        f = int(flags[bad[0]])
-        where = "reactor %d of %d (flags=0x%x)" % (bad[0], self.E, f)
-        if f & FLAG_DOMAIN:
-            raise ValueError("math domain error in " + where)
-        if f & FLAG_DIV0:
-            raise ZeroDivisionError("float division by zero in " + where)
-        if f & FLAG_OVERFLOW:
-            raise OverflowError("math range error in " + where)
-        if f & FLAG_STEP:
-            raise RuntimeError("adaptive step control failed (step underflow / max steps) in " + where)
-        if f & FLAG_NONFINITE:
-            raise FloatingPointError("state became NaN/Inf in " + where + " - step size too large?")
-        if f & FLAG_PRESSURE:
-            raise RuntimeError("model M2: the Newton sweeps of the pressure march did not converge in "
-                               + where + " - pass defines={'RMT_M2_NEWTON': 4} (pressure drop > 15 % of P)")
-        raise RuntimeError("device error in " + where)
+        err = flag_error(self.status())
+        if err is not None:
+            raise err
 
 
 class AutoStepper:
@@ -549,6 +597,7 @@ class AutoStepper:
         needed more than `auto-max-explicit-steps` steps is the last explicit one.
 
     Two devices (the on-chip RK45 geometry and the Rosenbrock kernel family) share the state tensor."""
+    stream_ordered = False                  # the host decides between two launches
 
     def __init__(self, dev_rk45, dev_ros4):
         """dev_ros4: the stiff device, or a zero-argument factory for it (single-process runs build - and JIT-
@@ -594,18 +643,18 @@ class AutoStepper:
     def raise_on_flags(self):
         self.last.raise_on_flags()
 
+    def last_geometry(self):
+        return self.last.last_geometry()
+
+    @property
+    def _stats(self):
+        return self.last._stats
+
     def _run(self, which, y, t0, t1, cfg, max_steps):
         dev = self.d45 if which == "rk45" else self.dr
-        first = not self._started[which]
+        rtol, atol, h0, _ = stepper_args(cfg, which, not self._started[which], auto=True)
         self._started[which] = True
-        if which == "rk45":
-            h0 = float(cfg.get('h0', DEVICE_DEFAULTS['rk45-h0']))
-            dev.rk45(y, t0, t1, float(cfg.get('rtol', DEVICE_DEFAULTS['auto-rk45-rtol'])),
-                     float(cfg.get('atol', DEVICE_DEFAULTS['auto-rk45-atol'])), h0 if first else -h0, int(max_steps))
-        else:
-            h0 = float(cfg.get('h0', DEVICE_DEFAULTS['ros4-h0']))
-            dev.ros4(y, t0, t1, float(cfg.get('rtol', DEVICE_DEFAULTS['ros4-rtol'])),
-                     float(cfg.get('atol', DEVICE_DEFAULTS['ros4-atol'])), h0 if first else -h0, int(max_steps))
+        getattr(dev, which)(y, t0, t1, rtol, atol, h0, int(max_steps))
         self.last = dev
         return dev
 
@@ -617,14 +666,13 @@ class AutoStepper:
         self.rhs_evals += int(np.sum(6*tried) + dev.E)
         done = bool(np.all(st["t_end"] >= t1))
         if not done:
-            flags = dev.status()            # read and clear: only the step budget may be set
-            other = flags & ~np.uint32(FLAG_STEP)
-            if other.any():                 # a genuine failure: put it back for the caller to raise
-                raise _flag_error(int(other[np.nonzero(other)[0][0]]), int(np.nonzero(other)[0][0]), dev.E)
+            err = flag_error(dev.status() & ~np.uint32(FLAG_STEP))       # read and clear: only the step budget may be set
+            if err is not None:             # a genuine failure
+                raise err
         return done, st
 
     def advance(self, y, t0, t1, cfg):
-        hard_max = int(cfg.get('max-steps', DEVICE_DEFAULTS['rk45-max-steps']))
+        hard_max = stepper_args(cfg, "ros4", False)[3]
         if self.mode != "ros4":
             backup = y.clone()
             if self.mode is None:
@@ -657,19 +705,6 @@ class AutoStepper:
         st = dev.rk45_stats()
         self.rhs_evals += int(np.sum((6 + dev.jacobian_evals)*(st["accepted"] + st["rejected"])))
         self.choices.append("ros4")
-
-
-def _flag_error(f, idx, E):
-    where = "reactor %d of %d (flags=0x%x)" % (idx, E, f)
-    if f & FLAG_DOMAIN:
-        return ValueError("math domain error in " + where)
-    if f & FLAG_DIV0:
-        return ZeroDivisionError("float division by zero in " + where)
-    if f & FLAG_OVERFLOW:
-        return OverflowError("math range error in " + where)
-    if f & FLAG_NONFINITE:
-        return FloatingPointError("state became NaN/Inf in " + where + " - step size too large?")
-    return RuntimeError("device error in " + where)
 
 
 # --------------------------------------------------------------------------- result packing
@@ -736,16 +771,10 @@ def _progress(i, total, quiet):
 
 
 def compile_mechanism(mech, N, fp32=False, block=None, npt=None, lds_state=None, defines=None,
-                      arch="gfx950", E=None, extra_opts=""):
+                      arch="gfx950", E=None, extra_opts="", features=()):
     """Code object for (mechanism, mesh size, members per rank) - what ensemble rank 0 compiles
-    and broadcasts; pass the same E/block/npt/lds_state/defines to N2Device(code=...)."""
-    b, n = choose_geometry(N, mech.V, fp32, E)
-    block, npt = int(block or b), int(npt or n)
-    defines, lds_state = kcache_choice(mech, N, fp32, block, npt, lds_state, defines)
-    tpl = hipbind.kernel_template()
-    return hipbind.compile_cached(mech.source(tpl, fp32, block, npt, lds_state, defines),
-                                  mech.digest(tpl, fp32, block, npt, lds_state, defines), arch,
-                                  compile_options(block, npt, (), extra_opts, defines))
+    and broadcasts; pass the same E/block/npt/lds_state/defines/features to N2Device(code=...)."""
+    return compile_plan(mech, fp32, code_plan(mech, N, fp32, E, block, npt, lds_state, defines, features), arch, extra_opts)
 
 
 def resolve_ivp(ivp):
@@ -816,28 +845,22 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     # Multi-rank: every rank-LOCAL phase (packing, the rank-0 compile inside DistributedEnsemble, loading the
     # module and allocating on the device) runs under ensemble.guarded / agree: a failure on one rank is raised
     # on every rank instead of leaving the others in the next collective until the backend's timeout.
-    from .ensemble import DistributedEnsemble, guarded
-    E_geo = max(sync.counts)                       # one geometry for all ranks (block sizes differ by <= 1 member)
-    b, n = choose_geometry(zNo, mech.V, fp32, E_geo)
-    block, npt = int(block or b), int(npt or n)
     defs = dict(defines or {})
-    for f in features:
-        defs[FEATURE_DEFINES[f]] = "1"
-    if "ros4" in features and "RMT_ROS_QUAD" not in defs and ros4_quad(mech, fp32) and npt == 1:
-        defs["RMT_ROS_QUAD"] = "1"
     if getattr(mech, "model", "N2") == "M2" and "RMT_M2_NEWTON" not in defs:
         sweeps = guarded(sync, lambda: plan.m2_newton_sweeps(
             np.array([pack(mi, mech, zNo)[1] for mi in inputs[sync.lo:sync.hi]]), mech, zNo))
         defs["RMT_M2_NEWTON"] = str(sync.max_int(sweeps))
     arch = device_arch()
-    # (a forced code object takes the ensemble's uniform fields as literals except the three its schedule moves)
-    lit = forced_literals if forcing is not None else (lambda mdef: mdef)
-    ens = DistributedEnsemble(
-        mech, inputs, zNo, group=sync.group, device=sync.device,
-        compile_fn=lambda mdef: compile_mechanism(mech, zNo, fp32, block, npt, None, {**defs, **lit(mdef)}, arch, E_geo))
+
+    def planned(mdef):      # one geometry for all ranks (block sizes differ by <= 1 member); the literals they agreed on
+        return code_plan(mech, zNo, fp32, max(sync.counts), block, npt, None, defs, features, literals=mdef)
+    ens = DistributedEnsemble(mech, inputs, zNo, group=sync.group, device=sync.device,
+                              compile_fn=lambda mdef: compile_plan(mech, fp32, planned(mdef), arch))
     rows = ens.rows if forcing is None else guarded(sync, forcing.attach, ens.rows, ens.named)
-    dev = guarded(sync, device_cls(), mech, rows, zNo, fp32=fp32, block=block, npt=npt,
-                  defines={**defs, **lit(ens.member_defines)}, specialize=False, code=ens.code, features=features)
+    # (the device re-derives the same record from its fields: code_plan leaves its own decisions alone)
+    cp = planned(ens.member_defines)
+    dev = guarded(sync, device_cls(), mech, rows, zNo, fp32=fp32, block=cp.block, npt=cp.npt, lds_state=cp.lds_state,
+                  defines=cp.defines, specialize=False, code=ens.code, features=features)
     if forcing is not None:
         guarded(sync, forcing.fix_mode, dev, "hip-ros4" if "ros4" in features else "explicit")
     return dev, ens.named, ens.IV
@@ -932,10 +955,10 @@ class Forcing:
         self.modes["ros4" if ivp == "hip-ros4" else "explicit"] = mode
 
     def refresh(self, dev, t0, t1, queued=False):
-        """the rows of the launch (t0, t1) onto the device; ``queued``: stream-ordered between the queued launches, returns
-        what has to stay alive until the stream got there"""
+        """the rows of the launch (t0, t1) onto the device; ``queued`` (a stream-ordered device): between the queued
+        launches, returns what has to stay alive until the stream got there"""
         rows = self.sched.forced_rows(self.rows, self.named, t0, t1)
-        if queued and hasattr(dev, "set_members_async"):
+        if queued:
             return dev.set_members_async(rows)
         dev.set_members(rows)
         return None
@@ -957,6 +980,7 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     (sample 0 before the first launch; with "residual" behind rmt_n2_rhs at that state).  Nothing is copied or
     synchronised per sample: the buffer comes back once, at the end, as ``stats["monitor-raw"]`` ([K][E_local][V][5];
     the callers pop it).  A run that raises on flags returns no monitor."""
+    import torch
     tNo = len(opTSpan) - 1
     # (t0, t1, index of the output time the launch ends at or None, index of the sample it ends at or None)
     launches = forcing.launches if forcing is not None else \
@@ -965,7 +989,6 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     nL = len(launches)
     mbuf = None
     if mon is not None:
-        import torch
         mbuf = torch.zeros((mon.K, y.shape[0], y.shape[1]//zNo, monitor.SLOTS), dtype=torch.float64, device=y.device)
 
     def sample(k):
@@ -974,8 +997,9 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     stats = {"steps": 0, "rhs_evals": 0, "node_steps": 0, "accepted": None, "rejected": None}
     if mon is not None:
         stats["launches"] = nL
-    _progress(0, tNo + 1, quiet)
-    def launch(i, t0, t1):
+    adaptive = ivp in ("hip-rk45", "hip-ros4", "hip-auto")
+
+    def step(i, t0, t1):
         if ivp == "hip-rk4":
             dt_req = float(cfg.get('dt', DEVICE_DEFAULTS['rk4-dt']))
             n = max(1, int(round((t1 - t0)/dt_req)))
@@ -991,115 +1015,68 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
             stats["rhs_evals"] += (2*n + 6) if ivp == "AM" else (n + 8)
         elif ivp == "hip-auto":
             dev.advance(y, t0, t1, cfg)
-        elif ivp == "hip-ros4":
-            # first interval: h0 for every reactor; later ones RESUME (h0 < 0): each reactor starts from
-            # the step its own controller proposed at the end of the previous interval (stats.h_last)
-            h0 = float(cfg.get('h0', DEVICE_DEFAULTS['ros4-h0']))
-            dev.ros4(y, t0, t1, float(cfg.get('rtol', DEVICE_DEFAULTS['ros4-rtol'])),
-                     float(cfg.get('atol', DEVICE_DEFAULTS['ros4-atol'])), h0 if i == 0 else -h0,
-                     int(cfg.get('max-steps', DEVICE_DEFAULTS['rk45-max-steps'])))
         else:
-            h0 = float(cfg.get('h0', DEVICE_DEFAULTS['rk45-h0']))
-            dev.rk45(y, t0, t1, float(cfg.get('rtol', DEVICE_DEFAULTS['rk45-rtol'])),
-                     float(cfg.get('atol', DEVICE_DEFAULTS['rk45-atol'])), h0 if i == 0 else -h0,
-                     int(cfg.get('max-steps', DEVICE_DEFAULTS['rk45-max-steps'])))
-        if check:
+            stepper = ivp[4:]                                    # "rk45" / "ros4"
+            getattr(dev, stepper)(y, t0, t1, *stepper_args(cfg, stepper, i == 0))
+
+    # One process, a stepper that needs no host decision between the intervals (a stream-ordered device): the launches of
+    # SEVERAL output intervals are queued back to back, each followed in the stream by the copy of its end state into
+    # pinned host memory (and of its step counters), and the host packs while the device integrates.  With a
+    # synchronisation per interval the device idled - and clocked down - while the host packed: 0.18 s for the bench's
+    # 256-member sweep against 0.04 s of kernel time.  The status words are sticky, so one look at the end of a batch
+    # raises what any of its launches flagged.  Batches are bounded by PIPELINE_BYTES of pinned memory.
+    # Every other run (multi-rank, "hip-auto", the host-emulation stand-in) is the same walk with batches of ONE launch
+    # and blocking copies; with ``sync`` the flags are read - and agreed on - inside the rank-local phase, ahead of the
+    # gather in on_interval.  (A device class that does not declare ``stream_ordered`` - a stand-in written before the
+    # attribute existed - is not: the synchronous walk asks nothing of it beyond the stepper and raise_on_flags.)
+    queued = sync is None and getattr(dev, "stream_ordered", False)
+    E_loc = y.shape[0]
+    per = E_loc*(y.shape[1]//zNo if outlet else y.shape[1])*y.element_size()
+    batch = int(max(1, min(nL, PIPELINE_BYTES//max(per, 1)))) if queued else 1
+
+    def to_host(src):
+        if not queued:
+            return src.cpu()
+        host = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
+        host.copy_(src, non_blocking=True)                       # stream-ordered: reads src before the next launch writes it
+        return host
+
+    def queue(lo, hi):
+        staged = []
+        for i in range(lo, hi):
+            t0, t1, kout, ksample = launches[i]
+            _progress(i + 1, nL + 1, quiet)
+            # (the page-locked rows of a queued refresh stay alive until the batch has landed)
+            rows = forcing.refresh(dev, t0, t1, queued) if forcing is not None else None
+            step(i, t0, t1)
+            sample(ksample)                                      # queued right behind its launch, into slice ksample
+            state = counters = landed = None
+            if kout is not None:
+                state = to_host(y.reshape(E_loc, -1, zNo)[:, :, zNo - 1] if outlet else y)
+            if adaptive:
+                counters = to_host(dev._stats)
+            if queued:
+                landed = torch.cuda.Event()
+                landed.record()
+            staged.append((kout, state, counters, landed, rows))
+        if sync is not None:
             dev.raise_on_flags()
+        return staged
 
-    check = True
-    adaptive = ivp in ("hip-rk45", "hip-ros4", "hip-auto")
-    # One process, a stepper that needs no host decision between the intervals: the launches of SEVERAL output intervals
-    # are queued back to back, each followed in the stream by the copy of its end state into pinned host memory (and of
-    # its step counters), and the host packs while the device integrates.  With a synchronisation per interval the device
-    # idled - and clocked down - while the host packed: 0.18 s for the bench's 256-member sweep against 0.04 s of kernel
-    # time.  The status words are sticky, so one look at the end of a batch raises what any of its launches flagged.
-    # Batches are bounded by PIPELINE_BYTES of pinned memory.
-    if sync is None and ivp != "hip-auto" and nL > 1 and getattr(y, "is_cuda", False) and hasattr(dev, "_stats"):
-        import torch
-        E_loc = y.shape[0]
-        per = E_loc*(y.shape[1]//zNo if outlet else y.shape[1])*y.element_size()
-        batch = int(max(1, min(nL, PIPELINE_BYTES//max(per, 1))))
-        check = False
-        sample(0)
-        for lo in range(0, nL, batch):
-            hi = min(nL, lo + batch)
-            hosts, counters, landed, staged = [], [], [], []
-            for i in range(lo, hi):
-                t0, t1, kout, ksample = launches[i]
-                _progress(i + 1, nL + 1, quiet)
-                if forcing is not None:                          # (the page-locked rows stay alive until the batch has landed)
-                    staged.append(forcing.refresh(dev, t0, t1, queued=True))
-                launch(i, t0, t1)
-                sample(ksample)                                  # queued right behind its launch, into slice ksample
-                host = None
-                if kout is not None:
-                    src = y.reshape(E_loc, -1, zNo)[:, :, zNo - 1] if outlet else y
-                    host = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
-                    host.copy_(src, non_blocking=True)           # stream-ordered: reads y before the next launch writes it
-                hosts.append(host)
-                if adaptive:
-                    c = torch.empty(dev._stats.shape, dtype=dev._stats.dtype, pin_memory=True)
-                    c.copy_(dev._stats, non_blocking=True)
-                    counters.append(c)
-                ev = torch.cuda.Event()
-                ev.record()
-                landed.append(ev)
-            for k, i in enumerate(range(lo, hi)):                 # packing interval i while the device is at i+1, i+2, ...
-                landed[k].synchronize()
-                if adaptive:
-                    raw = counters[k].numpy()
-                    acc, rej = raw[:, 2].copy().view(np.int64), raw[:, 3].copy().view(np.int64)
-                    stats["accepted"] = acc if stats["accepted"] is None else stats["accepted"] + acc
-                    stats["rejected"] = rej if stats["rejected"] is None else stats["rejected"] + rej
-                if hosts[k] is not None:
-                    on_interval(launches[i][2] - 1, float(opTSpan[launches[i][2]]), hosts[k].numpy().astype(np.float64))
-            dev.raise_on_flags()                                  # (sticky status words: whatever a launch of the batch flagged)
-            del staged
-        if mbuf is not None:
-            stats["monitor-raw"] = mbuf.cpu().numpy()             # the ONE copy of the monitor buffer
-        return finish_stats(stats, ivp, n_members, nL, zNo, dev.jacobian_evals)
-
-    if sync is None:
-        sample(0)
-    else:
-        err = None
-        try:
-            sample(0)
-        except Exception as e:                  # noqa: BLE001 - re-raised on every rank by agree()
-            err = e
-        sync.agree(err)
-    for i in range(nL):
-        t0, t1, kout, ksample = launches[i]
-        _progress(i + 1, nL + 1, quiet)
+    _progress(0, tNo + 1, quiet)
+    guarded(sync, sample, 0)
+    for lo in range(0, nL, batch):
+        for kout, state, counters, landed, _ in guarded(sync, queue, lo, min(nL, lo + batch)):
+            if landed is not None:                                # packing launch i while the device is at i+1, i+2, ...
+                landed.synchronize()
+            if counters is not None:
+                acc, rej = step_counts(counters.numpy())
+                stats["accepted"] = acc if stats["accepted"] is None else stats["accepted"] + acc
+                stats["rejected"] = rej if stats["rejected"] is None else stats["rejected"] + rej
+            if kout is not None:                                  # (None: a breakpoint or a sample time - nothing to pack)
+                on_interval(kout - 1, float(opTSpan[kout]), state.numpy().astype(np.float64))
         if sync is None:
-            if forcing is not None:
-                forcing.refresh(dev, t0, t1)
-            launch(i, t0, t1)
-            sample(ksample)
-        else:                                   # whatever goes wrong on one rank is raised on every rank
-            err = None
-            try:
-                if forcing is not None:
-                    forcing.refresh(dev, t0, t1)
-                launch(i, t0, t1)
-                sample(ksample)
-            except Exception as e:              # noqa: BLE001 - re-raised on every rank by agree()
-                err = e
-            sync.agree(err)
-        if adaptive:
-            st = dev.rk45_stats()
-            stats["accepted"] = st["accepted"] if stats["accepted"] is None else stats["accepted"] + st["accepted"]
-            stats["rejected"] = st["rejected"] if stats["rejected"] is None else stats["rejected"] + st["rejected"]
-        if kout is None:                        # a breakpoint: nothing to pack
-            continue
-        t1 = float(opTSpan[kout])
-        i = kout - 1
-        if outlet:
-            E_loc = y.shape[0]
-            Yh = y.reshape(E_loc, -1, zNo)[:, :, zNo - 1].contiguous().cpu().numpy().astype(np.float64)
-        else:
-            Yh = y.cpu().numpy().astype(np.float64)
-        on_interval(i, t1, Yh)
+            dev.raise_on_flags()                                  # (sticky status words: whatever a launch of the batch flagged)
     if ivp == "hip-auto":
         stats["method-per-interval"] = list(dev.choices)
     if mbuf is not None:
@@ -1128,28 +1105,71 @@ def attach_monitor(stats, mon, sync, convert):
     return [convert(e, raw[e]) for e in range(raw.shape[0])]
 
 
-def run_n2(modelInput, members_inputs=None):
-    """runN2 on the device.  ``members_inputs``: optional list of modelInput dicts (one per
-    ensemble member, same mechanism); default = the single reactor described by modelInput."""
+def steady_profiles(modelInput, members_inputs, pack, nout, defines=None, extra=None, handle_rows=None):
+    """What the steady-state models (n1.run_n1, steady.run_steady) share: pack the members' rows (``pack(mi, mech)`` ->
+    (named, row)), open an N2 handle of the module with the steady kernel family, ONE guarded launch of n1_profile, and
+    the gather of the profiles and step counts.  As one rank of a torch.distributed job a process integrates its
+    contiguous block of profiles; every rank-local phase (packing, device creation, the launch + status read) runs under
+    ensemble.guarded: a failure on one rank is raised on every rank before the next collective.
+    ``extra``: the model has S + extra unknowns (default: model N1's own count, N2Device.n1_profile);
+    ``handle_rows(inputs, mech)``: the handle's own N2 member rows where the steady rows do not serve (model N1).
+    Returns (mech, named of every member, U [E][nout][V1], {"accepted", "rejected"}) on the process that returns the
+    results (rank 0, or the only one), None on the other ranks."""
+    cfg = modelInput['solver-config']
+    all_inputs = list(members_inputs) if members_inputs else [modelInput]
+    mech = mechanism_for(modelInput, all_inputs, cfg)
+    sync = active_ranks(len(all_inputs)) if members_inputs else None
+    inputs = all_inputs if sync is None else all_inputs[sync.lo:sync.hi]
+
+    def pack_and_open():
+        pairs = [pack(mi, mech) for mi in inputs]
+        rows1 = np.ascontiguousarray(np.array([r for _, r in pairs]))
+        # the handle is an N2 handle of the same generated module; only its steady kernel is used
+        return pairs, rows1, device_cls()(mech, rows1 if handle_rows is None else handle_rows(inputs, mech), 64, block=64,
+                                          npt=1, specialize=False, features=("n1",), defines=defines)
+    pairs, rows1, dev = guarded(sync, pack_and_open)
+    try:
+        def launch():
+            out = dev.n1_profile(rows1, nout, float(cfg.get('rtol', DEVICE_DEFAULTS['n1-rtol'])),
+                                 float(cfg.get('atol', DEVICE_DEFAULTS['n1-atol'])), float(cfg.get('h0', 1e-6)),
+                                 int(cfg.get('max-steps', 10**7)), V1=None if extra is None else mech.S + extra)
+            dev.raise_on_flags()
+            return dev.rk45_stats(), out
+        stats, U = guarded(sync, launch)
+    finally:
+        dev.close()
+    if sync is not None:                    # rank 0 returns every member's profile, the other ranks None
+        U = sync.gather(U)
+        stats = {k: sync.gather(stats[k]) for k in ("accepted", "rejected")}
+        if U is None:
+            return None
+        pairs = [pack(mi, mech) for mi in all_inputs]
+    return mech, [nm for nm, _ in pairs], U, stats
+
+
+def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result, fp32=False, defines=None,
+                with_schedule=False, outlet=False, display=False):
+    """What run_n2 and m2.run_m2 share: the ranks of a torchrun job, the geometry of the `ivp`, the device(s), the walk
+    over the output intervals with the gather of every member's state on the process that returns the results, the
+    monitor, and the result with its "ensemble" / "ensemble-shard" entries.  The models hand in what differs:
+    ``pack`` / ``init`` (member constants and initial state), ``pack_all(Yg, named, mech, zNo, t1)`` (the dataPack entries
+    of all members at one output time; zNo = 1 with ``outlet``), ``result(dataPack, member input, zNo, opTSpan)`` (one
+    member's result dict), and whether fp32, "schedule", "ensemble-output" and "display-result" apply."""
     start = timer()
     cfg = modelInput['solver-config']
-    displayResult = cfg['display-result'] == "True"        # KeyError like the reference (:3337)
     ivp = resolve_ivp(cfg['ivp'])
-    zNo = int(cfg.get('zNo', solverSetting['N2']['zNo']))
-    tNo = int(cfg.get('tNo', solverSetting['N2']['tNo']))
-    fp32 = cfg.get('dtype', 'fp64') in ('fp32', 'float32')
+    setting = solverSetting['N2' if model == "N2" else 'S2']        # (runM2 reads S2: pbReactor.py:625, :694)
+    zNo, tNo = int(cfg.get('zNo', setting['zNo'])), int(cfg.get('tNo', setting['tNo']))
     quiet = bool(cfg.get('quiet', False))
     opT = modelInput['operating-conditions']['period']
-    modelId = modelInput['model']
-
-    plan.check_model_setting_n2()          # the reference's N2 RHS raises under any setting but "MAX" - so does this
+    opTSpan = np.linspace(0, opT, tNo + 1)
     inputs = list(members_inputs) if members_inputs else [modelInput]
     mech = mechanism_for(modelInput, inputs, cfg)
-    from .ensemble import active_ranks, guarded
     sync = active_ranks(len(inputs)) if members_inputs else None       # one rank of a torchrun job?
+    E_gpu = len(inputs) if sync is None else max(sync.counts)
     block, npt = cfg.get('block'), cfg.get('nodes-per-thread')
     # "schedule": time-varying inlet / coolant conditions (schedule.py); absent = None = exactly the run without it
-    sched = schedule.parse(modelInput, members_inputs, ivp)
+    sched = schedule.parse(modelInput, members_inputs, ivp) if with_schedule else None
     # "monitor": time series between the output times (monitor.py); absent = None = exactly the run without it
     mon = monitor.parse(modelInput, tNo)
     if mon is not None:
@@ -1166,71 +1186,81 @@ def run_n2(modelInput, members_inputs=None):
             # the geometry of ONE workgroup per reactor (no chunks: the chained kernels do not carry the forcing)
             block, npt = choose_geometry(zNo, mech.V, fp32)
     if ivp == "hip-ros4" and block is None:
-        block, npt = ros4_block(mech.V, zNo, fp32), 1
-    # "strict-flags": test the Python-exception conditions on every RK stage (default: stage 1 only)
-    defines = {"RMT_CHECK_ALL_STAGES": "1"} if cfg.get('strict-flags') else {}
+        block, npt = ros4_block(mech.V, zNo, fp32, ros4_quad(mech, fp32)), 1
+    defines = dict(defines or {})
     if ivp == "hip-rk45" and block is None:
-        if forcing is not None:
-            block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, chain=False)
-        else:
-            block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, E=len(inputs) if sync is None else max(sync.counts))
+        block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, **({"chain": False} if forcing is not None else {"E": E_gpu}))
         defines.update(geo_defs)
     if ivp == "hip-auto":
-        dev, named_local, IV = open_auto(mech, inputs, zNo, plan.member_constants, plan.initial_state, sync, fp32,
-                                         defines, block, npt, forcing=forcing)
+        dev, named_local, IV = open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block, npt, forcing=forcing)
     else:
-        dev, named_local, IV = open_members(mech, inputs, zNo, plan.member_constants, plan.initial_state, sync,
-                                            fp32=fp32, block=block, npt=npt, defines=defines,
-                                            features=("ros4",) if ivp == "hip-ros4" else (), forcing=forcing)
+        dev, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=block, npt=npt,
+                                            defines=defines, features=("ros4",) if ivp == "hip-ros4" else (),
+                                            forcing=forcing)
     # the process that returns the results (rank 0, or the only one) packs EVERY member
     packer = sync is None or sync.rank == 0
     try:
         if sync is None:
             named = named_local
         else:
-            named = guarded(sync, lambda: [plan.member_constants(mi, mech, zNo)[0] for mi in inputs] if packer else [])
+            named = guarded(sync, lambda: [pack(mi, mech, zNo)[0] for mi in inputs] if packer else [])
         y = guarded(sync, dev.to_device, IV)
         packs = [[] for _ in named]
-
-        outlet = outlet_only(cfg) if members_inputs else False
 
         def on_interval(i, t1, Yh):
             Yg = Yh if sync is None else sync.gather(Yh)               # [E_total][V*N] (or [V]: outlet) on rank 0
             if Yg is not None:
-                if len(named) == 1 and not outlet:
-                    packs[0].append(pack_interval(Yg[0], named[0], mech, zNo, t1, modelId))
-                else:
-                    for e, pk in enumerate(pack_intervals(Yg, named, mech, 1 if outlet else zNo, t1, modelId)):
-                        packs[e].append(pk)
-        stats = integrate_intervals(dev, y, cfg, ivp, np.linspace(0, opT, tNo + 1), len(named_local),
-                                    zNo, quiet or not packer, on_interval, sync, outlet, forcing, mon)
+                for e, pk in enumerate(pack_all(Yg, named, mech, 1 if outlet else zNo, t1)):
+                    packs[e].append(pk)
+        stats = integrate_intervals(dev, y, cfg, ivp, opTSpan, len(named_local), zNo, quiet or not packer, on_interval,
+                                    sync, outlet, forcing, mon)
         monitors = attach_monitor(stats, mon, sync, lambda e, raw: monitor.result_entry(
-            raw, mon.times, mech, zNo, named[e], "N2", residual=mon.residual))
+            raw, mon.times, mech, zNo, named[e], model, inputs[e]['reactor']['ReLe'], mon.residual))
         if forcing is not None:
             # which kernel forms ran: "reg" = the on-chip steppers, "mem" = the memory-resident ones; and what
             # rmt_n2_last_geometry reports for the last launch (workgroups per reactor, teams)
             stats["device-mode"] = dict(forcing.modes)
             stats.setdefault("launches", len(forcing.launches))       # (a monitored run: its refined list's)
-            last = getattr(dev, "last", dev)
-            if hasattr(last, "last_geometry"):
-                stats["last-geometry"] = last.last_geometry()
+            stats["last-geometry"] = dev.last_geometry()
     finally:
         dev.close()
-    elapsed = np.round(timer() - start, ROUND_FUN_ACCURACY)
-    resPack = {"computation-time": elapsed, "dataPack": packs[0] if packs else [], "device-stats": stats}
+    res = result(packs[0] if packs else [], modelInput, zNo, opTSpan)
+    res["computation-time"] = np.round(timer() - start, ROUND_FUN_ACCURACY)
+    res["device-stats"] = stats
     if sched is not None:
-        resPack["schedule"] = schedule.result_entry(sched, np.linspace(0, opT, tNo + 1)[1:])
+        res["schedule"] = schedule.result_entry(sched, opTSpan[1:])
     if members_inputs:
         # multi-rank: rank 0 holds the whole sweep, the other ranks None (and an empty dataPack)
-        resPack["ensemble"] = [{"dataPack": p} for p in packs] if packer else None
+        res["ensemble"] = [result(p, mi, zNo, opTSpan) for p, mi in zip(packs, inputs)] if packer else None
     if monitors:
-        resPack["monitor"] = monitors[0]
+        res["monitor"] = monitors[0]
         if members_inputs:
-            for entry, m in zip(resPack["ensemble"], monitors):
+            for entry, m in zip(res["ensemble"], monitors):
                 entry["monitor"] = m
     if sync is not None:
-        resPack["ensemble-shard"] = {"rank": sync.rank, "world": sync.world, "members": [sync.lo, sync.hi]}
-    if displayResult and packer:
+        res["ensemble-shard"] = {"rank": sync.rank, "world": sync.world, "members": [sync.lo, sync.hi]}
+    if display and packer:
         from .plotting import plot_results_dynamic
-        plot_results_dynamic(resPack, tNo)
-    return resPack
+        plot_results_dynamic(res, tNo)
+    return res
+
+
+def run_n2(modelInput, members_inputs=None):
+    """runN2 on the device.  ``members_inputs``: optional list of modelInput dicts (one per
+    ensemble member, same mechanism); default = the single reactor described by modelInput."""
+    cfg = modelInput['solver-config']
+    displayResult = cfg['display-result'] == "True"        # KeyError like the reference (:3337)
+    modelId = modelInput['model']
+    plan.check_model_setting_n2()          # the reference's N2 RHS raises under any setting but "MAX" - so does this
+    outlet = outlet_only(cfg) if members_inputs else False
+
+    def pack_all(Yg, named, mech, zNo, t1):
+        if len(named) == 1 and not outlet:
+            return [pack_interval(Yg[0], named[0], mech, zNo, t1, modelId)]
+        return pack_intervals(Yg, named, mech, zNo, t1, modelId)
+    return run_dynamic(modelInput, members_inputs, "N2", plan.member_constants, plan.initial_state, pack_all,
+                       lambda dataPack, mi, zNo, opTSpan: {"dataPack": dataPack},
+                       fp32=cfg.get('dtype', 'fp64') in ('fp32', 'float32'),
+                       # "strict-flags": test the Python-exception conditions on every RK stage (default: stage 1 only)
+                       defines={"RMT_CHECK_ALL_STAGES": "1"} if cfg.get('strict-flags') else {},
+                       with_schedule=True, outlet=outlet, display=displayResult)

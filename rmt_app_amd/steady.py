@@ -10,7 +10,7 @@ import numpy as np
 
 from . import plan
 from . import n2 as _n2
-from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
+from .settings import ROUND_FUN_ACCURACY, solverSetting
 
 SS_MODEL_DEFINE = {"M7": "7", "M1": "1"}
 # the methods the reference hands to solve_ivp ("default" = LSODA, pbReactor.py:270, :1294) and the device names
@@ -62,43 +62,16 @@ def run_steady(model, modelInput, members_inputs=None):
     if nout < 2:
         raise ValueError("zNo must be at least 2")
     pack = plan.member_constants_m7 if model == "M7" else plan.member_constants_m1
-    all_inputs = list(members_inputs) if members_inputs else [modelInput]
-    mech = _n2.mechanism_for(modelInput, all_inputs, cfg)
-    V1 = mech.S + (2 if model == "M7" else 3)
-    # as one rank of a torch.distributed job: this rank's contiguous block of profiles (see n1.run_n1)
-    from .ensemble import active_ranks, guarded
-    sync = active_ranks(len(all_inputs)) if members_inputs else None
-    inputs = all_inputs if sync is None else all_inputs[sync.lo:sync.hi]
-
-    def pack_and_open():
-        pairs = [pack(mi, mech) for mi in inputs]
-        rows1 = np.ascontiguousarray(np.array([r for _, r in pairs]))
-        # the handle is an N2 handle of the same generated module; only its steady kernel is used
-        return pairs, rows1, _n2.device_cls()(mech, rows1, 64, block=64, npt=1, specialize=False, features=("n1",),
-                                              defines={"RMT_SS_MODEL": SS_MODEL_DEFINE[model]})
-    pairs, rows1, dev = guarded(sync, pack_and_open)
-    try:
-        def launch():
-            out = dev.n1_profile(rows1, nout, float(cfg.get('rtol', DEVICE_DEFAULTS['n1-rtol'])),
-                                 float(cfg.get('atol', DEVICE_DEFAULTS['n1-atol'])), float(cfg.get('h0', 1e-6)),
-                                 int(cfg.get('max-steps', 10**7)), V1=V1)
-            dev.raise_on_flags()
-            return dev.rk45_stats(), out
-        stats, U = guarded(sync, launch)
-    finally:
-        dev.close()
-    if sync is not None:                    # rank 0 returns every member's result, the other ranks None
-        U = sync.gather(U)
-        stats = {k: sync.gather(stats[k]) for k in ("accepted", "rejected")}
-        if U is None:
-            return None
-        inputs = all_inputs
-        pairs = [pack(mi, mech) for mi in inputs]
+    got = _n2.steady_profiles(modelInput, members_inputs, pack, nout, {"RMT_SS_MODEL": SS_MODEL_DEFINE[model]},
+                              extra=2 if model == "M7" else 3)
+    if got is None:
+        return None
+    mech, named, U, stats = got
     elapsed = np.round(timer() - start, ROUND_FUN_ACCURACY)
     results = []
-    for e in range(len(inputs)):
-        Y = plan.unscale_steady(U[e], pairs[e][0], model, mech.S).T          # (V1, nout) like sol.y
-        r = result_dict(Y, pairs[e][0], mech, model)
+    for e in range(len(named)):
+        Y = plan.unscale_steady(U[e], named[e], model, mech.S).T          # (V1, nout) like sol.y
+        r = result_dict(Y, named[e], mech, model)
         r["computation-time"] = elapsed
         r["device-stats"] = {"accepted": int(stats["accepted"][e]), "rejected": int(stats["rejected"][e])}
         results.append(r)

@@ -12,6 +12,8 @@ CREATED = []          # (E, code-prefix, sorted defines) of every instance, for 
 
 
 class EmuDevice:
+    stream_ordered = False          # every call is synchronous: the walk takes one launch at a time
+
     def __init__(self, mech, members, N, fp32=False, block=None, npt=None, device=None, extra_opts="",
                  lds_state=None, defines=None, code=None, specialize=None, features=()):
         members = np.ascontiguousarray(members, dtype=np.float64)

@@ -860,3 +860,97 @@ def test_ros4_quad_layout_has_no_sweep_loop_spills():
         blk = [b for b in notes.split("- .agpr_count") if ".name:           %s" % kern in b or re.search(r"\.name:\s+%s\b" % kern, b)][0]
         scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
         assert scratch < 1024, (kern, scratch)           # the once-per-step Jacobian assembly still spills a little
+
+
+# ----------------------------------------------------------------------------- one plan for the code object of a run
+class _OneRank:
+    """What ensemble.RankSync gives n2.open_members, for a job whose one rank holds all E members (no process group)."""
+    group = device = None
+    rank, world = 0, 1
+
+    def __init__(self, E):
+        self.lo, self.hi, self.counts, self.n_total = 0, E, [E], E
+
+    def agree(self, err):
+        if err is not None:
+            raise err
+
+    def max_int(self, v):
+        return int(v)
+
+
+class _NoDevice:
+    """Stands where n2.N2Device is looked up: the routes are followed up to the compile, nothing is loaded."""
+
+    def __init__(self, mech, members, N, block=None, npt=None, **kw):
+        self.block, self.npt = block, npt
+
+    def set_mode(self, mode):
+        pass
+
+
+def _route_cases():
+    """(id, input factory, ivp, members E, nodes N, forced, explicit (block, npt) or None)"""
+    dme, syn12, m2 = INP.dme_notebook_input, INP.syn12_input, INP.m2_dme_input
+    return [("rk4-256x1024", dme, "hip-rk4", 256, 1024, False, None), ("rk4-64x1024", dme, "hip-rk4", 64, 1024, False, None),
+            ("rk4-8x20", dme, "hip-rk4", 8, 20, False, None), ("rk45-256x1024", dme, "hip-rk45", 256, 1024, False, None),
+            ("rk45-64x1024", dme, "hip-rk45", 64, 1024, False, None), ("ros4-dme-64x512", dme, "hip-ros4", 64, 512, False, None),
+            ("ros4-syn12-64x1024", syn12, "hip-ros4", 64, 1024, False, None),
+            ("forced-rk4-8x600", dme, "hip-rk4", 8, 600, True, None), ("forced-rk45-8x600", dme, "hip-rk45", 8, 600, True, None),
+            ("m2-ros4-8x100", m2, "hip-ros4", 8, 100, False, None),
+            ("ros4-dme-512x2-8x2048", dme, "hip-ros4", 8, 2048, False, (512, 2))]
+
+
+@pytest.mark.parametrize("case", _route_cases(), ids=lambda c: c[0])
+def test_single_process_and_multi_rank_routes_load_the_same_code_object(case, monkeypatch):
+    """The code object of a run is decided once (n2.code_plan): the single-process route (n2.precompile, what N2Device
+    compiles for the member rows) and the multi-rank route (the compile callback n2.open_members hands to
+    DistributedEnsemble, given the literals the ranks agreed on) ask hipbind.compile_cached for the identical
+    (cache key, hipRTC options).  The members differ in one column, so literals are in play; geometry and defines
+    are chosen per `ivp` as run_dynamic does."""
+    import copy
+    from rmt_app_amd import n2, schedule
+    from rmt_app_amd.ensemble import expand_members
+    _, make, ivp, E, N, forced, geometry = case
+    base = make(ivp=ivp)
+    if forced:
+        base["solver-config"]["schedule"] = {"time": [0.0, 0.25], "inlet-pressure": [5.0e6, 4.9e6]}
+    T0 = base["operating-conditions"]["temperature"]
+    inputs = expand_members(base, [{"operating-conditions": {"temperature": T0 + 0.05*e}} for e in range(E)])
+    mech = plan.Mechanism(base)
+    m2 = mech.model == "M2"
+    pack, init = (plan.member_constants_m2, plan.initial_state_m2) if m2 else (plan.member_constants, plan.initial_state)
+    block, npt = geometry or (None, None)
+    defines, features = {}, ()
+    if ivp == "hip-rk4" and forced:
+        block, npt = n2.choose_geometry(N, mech.V)
+    elif ivp == "hip-rk45":
+        block, npt, defines = n2.rk45_geometry(mech.V, N, **({"chain": False} if forced else {"E": E}))
+    elif ivp == "hip-ros4":
+        features = ("ros4",)
+        if block is None:
+            block, npt = n2.ros4_block(mech.V, N, False, n2.ros4_quad(mech)), 1
+    asked = []
+    monkeypatch.setattr(hipbind, "compile_cached",
+                        lambda src, key, arch="gfx950", opts="": asked.append((key, opts)) or b"\x7fELF")
+    monkeypatch.setattr(n2, "N2Device", _NoDevice)
+
+    def forcing():
+        sched = schedule.parse(base, inputs, ivp)
+        return n2.Forcing(sched, base["operating-conditions"]["period"], 2, N) if forced else None
+    # the single-process route: the rows open_members packs for one process, through precompile
+    pairs = [pack(mi, mech, N) for mi in inputs]
+    rows = np.array([r for _, r in pairs])
+    single_defs = dict(defines)
+    if forced:
+        rows = forcing().attach(rows, [nm for nm, _ in pairs])
+        single_defs["RMT_FORCING"] = "1"
+    assert np.sum(np.ptp(rows, axis=0) > 0) >= 1 and len(plan.uniform_member_defines(rows[:, :mech.row_width], mech.S)) > 0
+    key = n2.precompile(mech, rows, N, block=block, npt=npt, defines=single_defs, features=features)
+    single = list(asked)
+    del asked[:]
+    # the multi-rank route
+    n2.open_members(mech, inputs, N, pack, init, _OneRank(E), block=block, npt=npt, defines=copy.deepcopy(defines),
+                    features=features, forcing=forcing())
+    assert len(single) == 1 and len(asked) == 1 and single[0][0] == key
+    assert asked[0] == single[0], (single, asked)

@@ -70,11 +70,14 @@
 #ifndef RMT_NU
 #define RMT_NU 0
 #endif
-// RMT_FORCING 1 (solver-config "schedule", 11_forcing.inc): the member row grows by a tail of four doubles
+// RMT_FORCING 1 (solver-config "schedule", 11_forcing.inc): the member row grows by a tail of four doubles;
+// RMT_FORCING 2 (the schedule also moves the feed composition): by S more, the slopes of the inlet values M_CIN
 #ifndef RMT_FORCING
 #define RMT_FORCING 0
 #endif
-#if RMT_FORCING
+#if RMT_FORCING == 2
+#define RMT_NM (16 + RMT_S + RMT_NU + 4 + RMT_S)
+#elif RMT_FORCING
 #define RMT_NM (16 + RMT_S + RMT_NU + 4)
 #else
 #define RMT_NM (16 + RMT_S + RMT_NU)
@@ -107,6 +110,7 @@
 #define M_USER (16 + RMT_S)   // RMT_NU user parameters (always read at run time)
 #if RMT_FORCING
 #define M_FORCE (16 + RMT_S + RMT_NU)   // t_ref, d THETA_IN/dt, d P0/dt, d TM/dt of this launch (P0, THETA_IN, TM: the values at t_ref)
+#define M_FORCE_CIN (M_FORCE + 4)       // RMT_FORCING 2: d CIN_i/dt, S doubles (M_CIN: the values at t_ref)
 #endif
 
 typedef double preal;   // the pressure scan is always carried in fp64

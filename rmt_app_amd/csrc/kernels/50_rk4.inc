@@ -771,7 +771,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk4_mem(
 #pragma unroll
                 for (int i = 0; i < RMT_V; ++i) carry.up[i] = s_c.up[s][i];
 #if RMT_FORCING
-                rmt_forcing_apply(m, members + (size_t)e * RMT_NM, tstep + rmt_rk4_c(s) * h_);     // the wall temperature of this stage
+                rmt_forcing_apply3(m, members + (size_t)e * RMT_NM, tstep + rmt_rk4_c(s) * h_);    // the wall temperature of this stage (the inlet: s_c)
 #endif
                 if (s == 0 || RMT_CHECK_ALL_STAGES) rmt_rhs_block<RMT_NPT, true>(m, sh, ph, ys, nvalid, carry, k, flag);
                 else rmt_rhs_block<RMT_NPT, true>(m, sh, ph, ys, nvalid, carry, k, nof);

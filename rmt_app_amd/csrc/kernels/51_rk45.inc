@@ -136,7 +136,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_mem(
 #pragma unroll
                     for (int i = 0; i < RMT_V; ++i) carry.up[i] = s_c.up[s][i];
 #if RMT_FORCING
-                    rmt_forcing_apply(m, members + (size_t)e * RMT_NM, t + rmt_dp_c(s) * h);     // the wall temperature of this stage
+                    rmt_forcing_apply3(m, members + (size_t)e * RMT_NM, t + rmt_dp_c(s) * h);    // the wall temperature of this stage (the inlet: s_c)
 #endif
                     rmt_rhs_block<1, true>(m, sh, ph, ys, valid ? 1 : 0, carry, k, trial);
                     ph ^= 1;

@@ -120,14 +120,28 @@ KC_MAX_AGE = 1.3e-5     # ... RMT_KC_MAX_AGE: or sooner, so that no reference po
 
 def is_forced(defines):
     """True for the prelude defines of a code object that evaluates a schedule (csrc/kernels/11_forcing.inc): its member
-    rows carry schedule.TAIL more doubles and none of the forced fields is baked into the kernel."""
-    return str((defines or {}).get("RMT_FORCING", "0")) == "1"
+    rows carry schedule.TAIL more doubles ("1") or schedule.TAIL + S more ("2": the schedule also moves the feed
+    composition) and none of the forced fields is baked into the kernel."""
+    return forcing_level(defines) in ("1", "2")
 
 
-def forced_literals(member_defines):
-    """The sweep-invariant member fields a FORCED code object may take as literals: all but the three the schedule moves
-    (no RMT_MC_* literal may freeze a forced field; the others never change between the launches of a run)."""
-    return {k: v for k, v in member_defines.items() if k not in ("RMT_MC_THETA_IN", "RMT_MC_P0", "RMT_MC_TM")}
+def forcing_level(defines):
+    """The RMT_FORCING value of the prelude defines as a string: "0" (none), "1" or "2"."""
+    return str((defines or {}).get("RMT_FORCING", "0"))
+
+
+def forced_tail(defines, S):
+    """doubles a member row of that code object carries behind the ordinary 16 + S + NU"""
+    level = forcing_level(defines)
+    return schedule.TAIL + int(S) if level == "2" else schedule.TAIL if level == "1" else 0
+
+
+def forced_literals(member_defines, level="1"):
+    """The sweep-invariant member fields a FORCED code object may take as literals: all but the ones the schedule moves -
+    three for RMT_FORCING 1, the inlet composition as well for RMT_FORCING 2 (``level``) - no RMT_MC_* literal may freeze a
+    forced field; the others never change between the launches of a run."""
+    moved = ("RMT_MC_THETA_IN", "RMT_MC_P0", "RMT_MC_TM") + (("RMT_MC_CIN",) if str(level) == "2" else ())
+    return {k: v for k, v in member_defines.items() if k not in moved}
 
 
 def forced_mode(ivp, N, block, npt, want=None):
@@ -257,7 +271,7 @@ def code_plan(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None,
     if specialize:                            # sweep-invariant member fields become literals (frees SGPRs)
         literals = plan.uniform_member_defines(rows[:, :mech.row_width], mech.S)
     if literals:
-        defs.update(forced_literals(literals) if is_forced(defs) else literals)
+        defs.update(forced_literals(literals, forcing_level(defs)) if is_forced(defs) else literals)
     # "RMT_KCACHE": "1" (kcache_choice above, or the caller's own): the on-chip RK4 stepper caches the temperature-only
     # rate constants per node in LDS - that has to fit
     gen = plan.KCACHE_GEN[str(defs.get("RMT_KCACHE_GEN", "1"))]
@@ -388,8 +402,9 @@ class N2Device:
         if members.ndim == 1:
             members = members.reshape(1, -1)
         self.forced = is_forced(defines)
-        self.row_width = mech.row_width + (schedule.TAIL if self.forced else 0)
-        assert members.shape[1] == self.row_width, "member rows must hold 16 + S + NU doubles (+ 4 when forced)"
+        self.row_width = mech.row_width + forced_tail(defines, mech.S)
+        assert members.shape[1] == self.row_width, \
+            "member rows must hold 16 + S + NU doubles (+ 4 when forced, + 4 + S with a forced composition)"
         self.E = members.shape[0]
         self.members = members
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
@@ -406,7 +421,7 @@ class N2Device:
         p.n_species, p.n_reactions, p.n_vars = mech.S, mech.R, mech.V
         p.n_nodes, p.n_members, p.fp32 = self.N, self.E, int(self.fp32)
         p.block, p.nodes_per_thread = self.block, self.npt
-        p.n_user_params = self.row_width - plan.MEMBER_FIXED - mech.S       # (a forced row's tail travels as 4 more)
+        p.n_user_params = self.row_width - plan.MEMBER_FIXED - mech.S       # (a forced row's tail travels as 4 or 4 + S more)
         self.ros_quad = str(self.defines.get("RMT_ROS_QUAD", "0")) == "1"
         p.ros4_nodes_per_block = self.block//4 if self.ros_quad else 0
         p.code_object = C.cast(self._code, C.c_void_p)
@@ -828,10 +843,10 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     ensemble.RankSync): the rank's contiguous block; rank 0 compiles, every rank loads the broadcast
     code object, sweep-invariant member fields agreed over all ranks become kernel literals.
     Returns (device, named constants of the local members, local initial states [E_local][V*N]).
-    ``forcing`` (a Forcing, solver-config "schedule"): the code object is generated with RMT_FORCING, the rows get their
-    tail, and the host fixes the kernel form (forced_mode)."""
+    ``forcing`` (a Forcing, solver-config "schedule"): the code object is generated with RMT_FORCING (2 when the schedule
+    moves the feed composition, else 1), the rows get their tail, and the host fixes the kernel form (forced_mode)."""
     if forcing is not None:
-        defines = {**(defines or {}), "RMT_FORCING": "1"}
+        defines = {**(defines or {}), "RMT_FORCING": forcing.sched.forcing_level}
     if sync is None:
         pairs = [pack(mi, mech, zNo) for mi in inputs]
         rows = np.array([r for _, r in pairs])

@@ -434,6 +434,23 @@ def forced_slopes(named, slopes):
     return np.stack([slopes[:, 0]/tf, slopes[:, 1], slopes[:, 2]], axis=1)
 
 
+def forced_composition(rows, named, conc):
+    """solver-config "schedule", "inlet-concentration": write the forced inlet concentrations [E][S] (unit of
+    feed["concentration"]) into the member rows in place - CIN_i(t) = C_in,i(t)/Cmax (:4090) with the member's OWN Cmax =
+    max(feed concentration at t = 0): the scaling of the state does not move with the disturbance."""
+    F = MEMBER_FIELDS
+    conc = np.asarray(conc, dtype=np.float64)
+    cmax = np.array([nm["Cmax"] for nm in named], dtype=np.float64)
+    rows[:, F["CIN"]:F["CIN"] + conc.shape[1]] = conc/cmax[:, None]
+    return rows
+
+
+def forced_composition_slopes(named, slopes):
+    """d/dt of CIN from the slopes [E][S] of the inlet concentrations: the last S doubles of a forced member row."""
+    cmax = np.array([nm["Cmax"] for nm in named], dtype=np.float64)
+    return np.asarray(slopes, dtype=np.float64)/cmax[:, None]
+
+
 def member_constants_m2(modelInput, mech, zNo):
     """Model M2 (pbReactor.py:552-700 setup, :845-1165 RHS): the packed row keeps the N2 layout
     (MEMBER_FIELDS) with the meanings listed above the M2 node functions in csrc/kernels/21_node_m2.inc."""

@@ -5,9 +5,9 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
-coolant conditions, G13).
+coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
 """
@@ -833,6 +833,155 @@ def g_schedule(which=None):
         print("G13 %s written (%.0f s)" % (name, time.time() - t0))
 
 
+# --------------------------------------------------------------------------- G14
+# Time-varying feed composition (solver-config "schedule", key "inlet-concentration").  Every disturbance keeps H2, the
+# largest feed concentration, fixed: the reference takes its scaling from max(constBC1['SpCoi0']) (pbHomoReactor.py:3901,
+# 4090), so only then is "replace constBC1['SpCoi0']" the same model as a boundary value that moves under a fixed
+# scaling.  The cases are written to g14_feed.json; nothing of the product is imported, the piecewise-linear functions
+# are restated (vector-valued) below.
+G14_FEED = [574.8978, 287.4489, 0.0115, 287.4489, 0.0115, 0.0115]       # dme_nb: H2, CO2, H2O, CO, CH3OH, DME
+G14_NEW = [574.8978, 250.0, 0.0115, 324.8978, 0.0115, 0.0115]           # CO2 -37.4489, CO +37.4489
+G14_STEP = lambda ts: {"time": [0.0, ts, ts, 0.4], "inlet-concentration": [G14_FEED, G14_FEED, G14_NEW, G14_NEW]}  # noqa: E731
+G14_CASES = {
+    "FA": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2, "schedule": G14_STEP(0.2)},
+    "FA1": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 4, "schedule": G14_STEP(0.23)},
+    "FB": {"input": "dme_nb", "zNo": 20, "period": 0.3, "tNo": 6,
+           "schedule": {"time": [0.0, 0.1, 0.2, 0.3], "inlet-concentration": [G14_FEED, G14_FEED, G14_NEW, G14_NEW],
+                        "inlet-temperature": [523.0, 523.0, 533.0, 533.0]}},
+    "FC": {"input": "dme_nb", "zNo": 600, "period": 0.06, "tNo": 3, "method": "DOP853",
+           "schedule": {"time": [0.0, 0.02, 0.04, 0.06], "inlet-concentration": [G14_FEED, G14_FEED, G14_NEW, G14_NEW]}},
+    "FD": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2, "members": [0, 15, 31],
+           "ensemble": {"temperature": [513.0, 516.0, 519.0, 522.0, 525.0, 528.0, 531.0, 534.0],
+                        "pressure": [4.0e6, 4.5e6, 5.0e6, 5.5e6]},
+           "schedule": {"time": [0.0, 0.2, 0.2, 0.4], "relative": True,
+                        "inlet-concentration": [[0.0]*6, [0.0]*6, [0.0, -30.0, 0.0, 30.0, 0.0, 0.0],
+                                                [0.0, -30.0, 0.0, 30.0, 0.0, 0.0]]}},
+}
+
+
+def _pwv_piece(times, vals, a, b):
+    """(values at a, slopes) of the linear piece that holds over (a, b); vals [K] or [K][S]."""
+    T = np.asarray(times, dtype=float)
+    vals = np.asarray(vals, dtype=float)
+    k = int(np.searchsorted(T, 0.5*(a + b), side="right")) - 1
+    if k >= len(T) - 1:
+        return vals[-1].copy(), np.zeros_like(vals[-1])
+    s = (vals[k + 1] - vals[k])/(T[k + 1] - T[k])
+    return vals[k] + s*(a - T[k]), s
+
+
+def _pwv_right(times, vals, t):
+    """values at t; at a jump the ones that hold from t on; vals [K] or [K][S]."""
+    T = np.asarray(times, dtype=float)
+    vals = np.asarray(vals, dtype=float)
+    k = int(np.searchsorted(T, t, side="right")) - 1
+    if k >= len(T) - 1:
+        return vals[-1].copy()
+    return vals[k] + (vals[k + 1] - vals[k])*(t - T[k])/(T[k + 1] - T[k])
+
+
+def g14_trajectory(case, member=None, rtol=1e-10, atol=1e-13):
+    """Whole states at the output times: SciPy on the oracle's vectorised RHS with SpCoi0 (and T0, P0, Tm where the case
+    schedules them) as functions of t, restarted at every breakpoint.  The oracle's scaling is max(SpCoi0), which no case
+    moves (asserted)."""
+    from oracle import n2_oracle as O
+    mi = _g13_member_input(case, member)
+    pr = dict(O.setup_n2(mi, zNo=case["zNo"]))
+    f = O.make_rhs_vec(pr)
+    sch = case["schedule"]
+    own = {"T0": pr["T0"], "P0": pr["P0"], "Tm": pr["Tm"], "SpCoi0": np.array(pr["SpCoi0"], dtype=float)}
+    cmax = float(np.max(own["SpCoi0"]))
+    vals = {}
+    for key, name in G13_KEYS + (("inlet-concentration", "SpCoi0"),):
+        if sch.get(key) is not None:
+            v = np.asarray(sch[key], dtype=float)
+            vals[name] = own[name] + v if sch.get("relative") else v
+    assert np.all(np.max(vals["SpCoi0"], axis=1) == cmax), "the disturbance must leave max(SpCoi0) unchanged"
+    out_t = np.linspace(0.0, case["period"], case["tNo"] + 1)
+    marks = sorted(set(out_t.tolist()) | {b for b in sch["time"] if 0 < b < case["period"]
+                                          and np.min(np.abs(out_t - b)) > 1e-12*case["period"]})
+    y = np.array(pr["IV"], dtype=float)
+    states, nfev = [], 0
+    method = case.get("method", "LSODA")
+    for a, b in zip(marks[:-1], marks[1:]):
+        piece = {name: _pwv_piece(sch["time"], v, a, b) for name, v in vals.items()}
+
+        def ft(t, yy, piece=piece, a=a):
+            for name, (v0, s) in piece.items():
+                pr[name] = v0 + s*(t - a)
+            return f(t, yy)
+        t0 = time.time()
+        sol = REAL_SOLVE_IVP(ft, (a, b), y, method=method, rtol=rtol, atol=atol)
+        if not sol.success:
+            raise RuntimeError(sol.message)
+        y = sol.y[:, -1]
+        nfev += sol.nfev
+        print("G14 %s%s: (%.4f, %.4f) nfev=%d %.0f s" % (case.get("name", ""), "" if member is None else " member %d" % member,
+                                                          a, b, sol.nfev, time.time() - t0), flush=True)
+        if np.min(np.abs(out_t - b)) <= 1e-12*case["period"]:
+            states.append(y.copy())
+    return out_t[1:], np.array(states), nfev
+
+
+def g14_probes():
+    """The reference's own modelEquationN2 with only constBC1['SpCoi0'] replaced by the forced composition (one probe
+    also with constBC1['T0']): before, inside (two times) and after the ramp of schedule FB, and before and behind the
+    step of schedule FA; the six G13 probe states each."""
+    import copy
+    mi = INP.dme_notebook_input()
+    IV, params = capture(mi, 20)
+    V = params[2]["const"]["varNo"]
+    Y = np.array([IV] + synthetic_states(IV, V, 20, seed=13) + synthetic_states(IV, V, 20, seed=131)[:2])
+    assert len(Y) == 6
+    probes = [("FB", t) for t in (0.05, 0.125, 0.15, 0.25)] + [("FA", t) for t in (0.1, 0.2)]
+    conc, forced, F = [], [], []
+    for name, t in probes:
+        sch = G14_CASES[name]["schedule"]
+        v = {"T0": 523.0, "P0": 5.0e6, "Tm": 523.0}
+        for key, nm in G13_KEYS:
+            if sch.get(key) is not None:
+                v[nm] = float(_pwv_right(sch["time"], sch[key], t))
+        c = _pwv_right(sch["time"], sch["inlet-concentration"], t)
+        p2 = list(params)
+        p2[2] = copy.deepcopy(params[2])
+        p2[2]["constBC1"]["SpCoi0"] = np.array(c, dtype=float)
+        p2[2]["constBC1"]["T0"] = v["T0"]
+        p2[2]["constBC1"]["P0"] = v["P0"]
+        p2[2]["ExHe"]["MeTe"] = v["Tm"]
+        conc.append(c)
+        forced.append([v["T0"], v["P0"], v["Tm"]])
+        F.append([rhs(tuple(p2), y) for y in Y])
+    np.savez_compressed(os.path.join(GOLD, "g14_feed_probes.npz"), y=Y, f=np.array(F), conc=np.array(conc),
+                        forced=np.array(forced), times=np.array([t for _, t in probes]),
+                        case=np.array([n for n, _ in probes]))
+    print("G14 probes written")
+
+
+def g_feed(which=None):
+    with open(os.path.join(GOLD, "g14_feed.json"), "w") as f:
+        json.dump({"cases": G14_CASES, "rtol": 1e-10, "atol": 1e-13,
+                   "reference": "SciPy LSODA (case FC: DOP853) on oracle.n2_oracle.make_rhs_vec with SpCoi0(t), restarted "
+                                "at breakpoints; max(SpCoi0) stays fixed"}, f, indent=1)
+    todo = [which] if which else ["probes", "FA", "FA1", "FB", "FC", "FD"]
+    for name in todo:
+        if name == "probes":
+            g14_probes()
+            continue
+        case = dict(G14_CASES[name], name=name)
+        out = {}
+        t0 = time.time()
+        if "members" in case:
+            for m in case["members"]:
+                times, states, nfev = g14_trajectory(case, m)
+                out["states_%d" % m] = states
+        else:
+            times, states, nfev = g14_trajectory(case)
+            out["states"] = states
+        np.savez_compressed(os.path.join(GOLD, "g14_feed_%s.npz" % name), times=times, nfev=nfev,
+                            wall_s=time.time() - t0, **out)
+        print("G14 %s written (%.0f s)" % (name, time.time() - t0))
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -862,6 +1011,8 @@ def main(argv):
             g_steady(what.upper())
         elif what == "schedule" or what.startswith("schedule="):
             g_schedule(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "feed" or what.startswith("feed="):
+            g_feed(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

@@ -6,11 +6,15 @@
   rows and the forcing evaluated at every stage);
 * wall time and step counts of the 256 x 1024 x 0.5 s hip-ros4 job through rmtExe, without a schedule and with case A's
   step (at t = 0.2: MeTe +10 K, T_in +5 K, P_in -2 % of the base pressure) as a relative schedule;
-* VGPR / AGPR / scratch of the forced against the unforced builds (rmt_app_amd.isa.kernel_resources).
+* the same two figures with a scheduled feed composition ("inlet-concentration", RMT_FORCING 2): rmt_n2_rk4_reg with a
+  ramp of T_in, MeTe AND the composition against the RMT_FORCING 1 rate of the same session, and the hip-ros4 job with a
+  composition step at t = 0.2 (CO2 -30, CO +30 mol/m^3, relative) against the job with case A's step;
+* VGPR / AGPR / SGPR / scratch of the builds with RMT_FORCING 0, 1 and 2 (rmt_app_amd.isa.kernel_resources).
 
 usage: schedule_bench.py [--steps 2000] [--members 256] [--nodes 1024] [--skip-ros4]
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -37,14 +41,15 @@ def sweep(members):
 def resources(mech, block, npt, defs, kernels, features=()):
     tpl = hipbind.kernel_template()
     out = {}
-    for forced in (False, True):
-        d = dict(defs, **({"RMT_FORCING": "1"} if forced else {}))
+    for level, tag in (("0", "unforced"), ("1", "forced"), ("2", "forced+composition")):
+        d = dict(defs, **({"RMT_FORCING": level} if level != "0" else {}))
         blob = hipbind.compile_cached(mech.source(tpl, False, block, npt, None, d), mech.digest(tpl, False, block, npt, None, d),
                                       "gfx950", n2.compile_options(block, npt, features, "", d))
         for k in kernels:
             r = isa.kernel_resources(blob, k)
-            out["%s %dx%d %s" % (k, block, npt, "forced" if forced else "unforced")] = {
-                "vgpr": r.get("vgpr_count"), "agpr": r.get("agpr_count"), "scratch": r.get("private_segment_fixed_size")}
+            out["%s %dx%d %s" % (k, block, npt, tag)] = {
+                "vgpr": r.get("vgpr_count"), "agpr": r.get("agpr_count"), "sgpr": r.get("sgpr_count"),
+                "scratch": r.get("private_segment_fixed_size")}
     return out
 
 
@@ -90,13 +95,27 @@ def main():
     dev.set_mode("reg")
     fo = rk4_rate(dev, y0, dt, a.steps)
     dev.close()
+    # ... and with the feed composition ramped as well (RMT_FORCING 2; CO2 -30, CO +30 mol/m^3 over the same second)
+    feed_off = [0.0, -30.0, 0.0, 30.0, 0.0, 0.0]
+    ramp2 = copy.deepcopy(ramp)
+    ramp2["solver-config"]["schedule"]["inlet-concentration"] = [[0.0]*6, feed_off]
+    sch2 = schedule.parse(ramp2, members)
+    dev = n2.N2Device(mech, sch2.forced_rows(rows, named, 0.0, dt*a.steps), N, block=512, npt=2,
+                      defines={"RMT_FORCING": sch2.forcing_level})
+    dev.set_mode("reg")
+    fc = rk4_rate(dev, y0, dt, a.steps)
+    dev.close()
     out["rk4_reg_node_steps_per_s"] = {"unforced": float(np.median(un)), "forced": float(np.median(fo)),
-                                       "unforced_repeats": un, "forced_repeats": fo,
-                                       "forced_over_unforced": float(np.median(fo)/np.median(un))}
+                                       "forced_composition": float(np.median(fc)),
+                                       "unforced_repeats": un, "forced_repeats": fo, "forced_composition_repeats": fc,
+                                       "forced_over_unforced": float(np.median(fo)/np.median(un)),
+                                       "composition_over_forced": float(np.median(fc)/np.median(fo))}
     # --- the stiff job through rmtExe
     if not a.skip_ros4:
         job = {}
-        for tag, spec in (("unscheduled", None), ("case_A_step", step_a)):
+        step_feed = {"time": [0.0, 0.2, 0.2, 0.5], "relative": True,
+                     "inlet-concentration": [[0.0]*6, [0.0]*6, feed_off, feed_off]}
+        for tag, spec in (("unscheduled", None), ("case_A_step", step_a), ("case_FA_feed_step", step_feed)):
             mi = dict(base, **{"solver-config": dict(base["solver-config"], ensemble=ens)})
             if spec is not None:
                 mi["solver-config"]["schedule"] = spec

@@ -74,6 +74,20 @@ extern "C" {
  * fp64 division and exp of the kernels turn an intermediate inf into NaN - 1/(1+inf) is NaN, not 0 - so
  * the usual ways of mapping an overflow back to a finite rate do poison it).  Code objects
  * generated with RMT_CHECK_ALL_STAGES=1 (solver-config "strict-flags") test every stage.
+ * Dynamic range of the generated rate laws (fp64 code objects without a node Jacobian): divisions whose
+ * denominators do not depend on each other share ONE reciprocal, of the product of up to four denominators
+ * (rmt_app_amd/lowering.py div_groups).  That product can overflow or underflow where each quotient alone
+ * would not (four denominators near 1e-80, say).  The device reciprocal refines v_rcp_f64 by Newton steps,
+ * which turn the reciprocal of an overflowed (inf) or underflowed (0) product into NaN: the rates are then
+ * non-finite and the reactor ends in RMT_N2_FLAG_NONFINITE instead of carrying a wrong number; the
+ * division-by-zero test still runs on every denominator itself.  This holds for that reciprocal only: a plain
+ * 1.0/b gives 0 for an overflowed product, so the rates can come out finite and wrong without a flag - the
+ * case of the host emulation of the generated source (oracle/hostemu.py), which mirrors the default emission.
+ * Code objects built with RMT_FAST_MATH=0 and fp32 code objects (v_rcp_f32, no Newton step, range 1e+-38)
+ * never share reciprocals.  The generator switch RMT_DIV_BATCH=0 (a define handed to
+ * plan.Mechanism.source; the kernel source does not read it) keeps one reciprocal per division everywhere.
+ * Product species clamped at 1e-30, the start of a reactor fed without products, give a product near 1e-52:
+ * far inside the fp64 range.
  * Every entry point taking a handle runs on the device that was current at rmt_n2_create and
  * restores the caller's current device before returning. */
 

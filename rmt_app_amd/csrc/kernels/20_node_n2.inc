@@ -1,5 +1,21 @@
 #if RMT_MODEL == 0
 // ------------------------------------------------------------------ node physics
+// Two cuts of the node function's multiplications (each its own switch, default on; profiles/node_cuts.md):
+//  RMT_NODE_CONV_FOLD     the convective term as (F1 inv_dz)(up - y): the product is a per-reactor constant - a literal
+//                         where the member fields are literals (RMT_MC_*), else formed once per call
+//  RMT_NODE_X_FROM_STATE  x_i = cc_i / sum cc from the clamped state itself (C_i = cmax cc_i scales numerator and
+//                         denominator alike), only where the kinetics never read C (RMT_KIN_USES_C 0, from the lowering)
+//                         and the unit has no rmt_node_jac (the stiff stepper differentiates x_i = C_i / sum C as written)
+#ifndef RMT_NODE_CONV_FOLD
+#define RMT_NODE_CONV_FOLD 1
+#endif
+#ifndef RMT_NODE_X_FROM_STATE
+#define RMT_NODE_X_FROM_STATE 1
+#endif
+#ifndef RMT_KIN_USES_C
+#define RMT_KIN_USES_C 1
+#endif
+#define RMT_NODE_X_CC (RMT_NODE_X_FROM_STATE && !RMT_KIN_USES_C && !RMT_WITH_ROS4)
 // Phase A (before the pressure scan): clamp, real concentrations, mole fractions, T, mixture MW,
 // Ergun affine coefficient.  pbHomoReactor.py:3897-3928, 3960-3979.
 struct RmtNode {
@@ -13,12 +29,22 @@ struct RmtNode {
 __device__ __forceinline__ preal rmt_node_pre(const RmtMember& m, const real* __restrict__ ys,
                                               RmtNode& nd) {
     real ctot = real(0);
+#if RMT_NODE_X_CC
+    real cs[RMT_S];                                       // ctot, inv_ctot below: of the clamped state (no cmax)
+#pragma unroll
+    for (int i = 0; i < RMT_S; ++i) {
+        cs[i] = rmt_max(ys[i], RMT_EPS);                  // :3899
+        nd.C[i] = cs[i] * m.cmax;                         // :3903 (MAX scaling; no reader here: removed)
+        ctot += cs[i];
+    }
+#else
 #pragma unroll
     for (int i = 0; i < RMT_S; ++i) {
         const real cc = rmt_max(ys[i], RMT_EPS);          // :3899
         nd.C[i] = cc * m.cmax;                            // :3903 (MAX scaling)
         ctot += nd.C[i];
     }
+#endif
 #if RMT_ISO
     nd.T = m.tf;
 #else
@@ -40,7 +66,11 @@ __device__ __forceinline__ preal rmt_node_pre(const RmtMember& m, const real* __
     real mw = real(0);
 #pragma unroll
     for (int i = 0; i < RMT_S; ++i) {
+#if RMT_NODE_X_CC
+        nd.x[i] = cs[i] * inv_ctot;                       // :3927
+#else
         nd.x[i] = nd.C[i] * inv_ctot;                     // :3927
+#endif
         mw += nd.x[i] * RMT_MW[i];
     }
     nd.M = mw * real(1e-3);                               // :3960  [kg/mol]
@@ -61,12 +91,23 @@ __device__ __forceinline__ void rmt_node_post(const RmtMember& m, const RmtNode&
     const real P = real(Pz);
     // (1) convective parts first: after this the stage state and the upstream values are dead,
     //     which keeps the register footprint of the kinetics small.
+#if RMT_NODE_CONV_FOLD
+    const real conv = m.f1 * m.inv_dz;
+#pragma unroll
+    for (int i = 0; i < RMT_S; ++i)
+        k[i] = conv * (up[i] - ys[i]);                                  // :4086-4098, convective term
+#else
 #pragma unroll
     for (int i = 0; i < RMT_S; ++i)
         k[i] = -m.f1 * ((ys[i] - up[i]) * m.inv_dz);                    // :4086-4098, convective term
+#endif
 #if !RMT_ISO
     const real T = nd.T;
+#if RMT_NODE_CONV_FOLD
+    k[RMT_S] = (m.ft * m.inv_dz) * (up[RMT_S] - ys[RMT_S]);             // :4104-4116
+#else
     k[RMT_S] = -m.ft * ((ys[RMT_S] - up[RMT_S]) * m.inv_dz);            // :4104-4116
+#endif
     // (2) everything of the energy balance that does not need the rates
     real hq[RMT_R];
     real cpm = real(0);

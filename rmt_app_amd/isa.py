@@ -50,6 +50,7 @@ def _mix(ins):
         "instructions": len(ins),
         "valu": sum(v for k, v in c.items() if k.startswith("v_")),
         "valu_f64": sum(v for k, v in c.items() if k.startswith("v_") and "f64" in k),
+        "rcp_f64": sum(v for k, v in c.items() if k.startswith("v_rcp_f64")),
         "salu": sum(v for k, v in c.items() if k.startswith("s_")),
         "s_mov": c["s_mov_b32"] + c["s_mov_b64"],
         "lane_moves": c["v_readlane_b32"] + c["v_writelane_b32"],

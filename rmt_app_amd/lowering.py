@@ -737,6 +737,62 @@ class Lowered:
         partial = [{k: v.i for k, v in d[o].items()} for o in self.outputs]
         return Gradient(g2, [new[o].i for o in self.outputs], partial, self.S, n_primal, wrt)
 
+    # ---- one reciprocal for independent divisions
+    DIV_BATCH_CAP = 4
+
+    def div_groups(self, cap=None):
+        """Divisions of the DAG that can share ONE reciprocal: lists of ``div`` / ``rcp`` node ids (id order, at least two,
+        at most ``cap`` = DIV_BATCH_CAP each).  v_rcp_f64 issues at a quarter of the FMA rate and every reciprocal carries
+        its Newton steps, so n reciprocals 1/d_1 .. 1/d_n are cheaper as a prefix-product inversion: p_k = d_1 .. d_k,
+        t = 1/p_n, then 1/d_k = t_k p_(k-1), t_(k-1) = t_k d_k going down - one reciprocal and 3(n-1) multiplications.
+
+        A division joins a group only when its denominator exists before the group's FIRST division (node ids are
+        creation-ordered, so such a denominator cannot depend on any member's result); the group's reciprocals are
+        printed right there, at its first division - no denominator is evaluated earlier than in the plain emission.
+        Left alone: constant denominators, 1/T (comes with the node state) and temperature-only denominators (they
+        belong to the cached section of a caching stepper, see kcache_plan).
+
+        Dynamic range: the product of up to four denominators can overflow or underflow where each quotient alone
+        would not.  With the fp64 device rmt_rcp (its Newton steps turn rcp(inf) and rcp(0) into NaN) the rates are then
+        non-finite and the reactor ends in FLAG_NONFINITE.  A plain 1.0/b (host emulation, RMT_FAST_MATH 0) and
+        v_rcp_f32 return 0 for an overflowed product: finite, wrong rates without a flag - which is why
+        plan.Mechanism.source never asks for the pass in fp32 (include/rmt_n2.h has the figures).
+        ``emit(div_batch=False)`` (plan.Mechanism.source with RMT_DIV_BATCH 0 among its defines: a switch of the
+        generator, the kernel source never reads it) keeps one reciprocal per division."""
+        g = self.g
+        cap = self.DIV_BATCH_CAP if cap is None else int(cap)
+        tonly = {}
+        for i in sorted(self.live):
+            op, a, b = g.nodes[i]
+            if op == "const":
+                tonly[i] = True
+            elif op == "in":
+                tonly[i] = (a == "T")
+            else:
+                tonly[i] = tonly[a] and (b is None or op == "powi" or tonly[b])
+        groups = []
+        for i in sorted(self.live):
+            op, a, b = g.nodes[i]
+            if op not in ("div", "rcp"):
+                continue
+            d = b if op == "div" else a
+            if tonly[d]:
+                continue
+            for grp in groups:
+                if len(grp) < cap and d < grp[0]:
+                    grp.append(i)
+                    break
+            else:
+                groups.append([i])
+        return [grp for grp in groups if len(grp) >= 2]
+
+    def denominator(self, i):
+        """the node a ``div`` / ``rcp`` node divides by"""
+        op, a, b = self.g.nodes[i]
+        if op not in ("div", "rcp"):
+            raise ValueError("node %d is no division" % i)
+        return b if op == "div" else a
+
     # ---- HIP C++ emission
     def _emitter(self, nocheck_from=None):
         """-> emit(i, name, declare=True, nocheck=False): lines of HIP C++ for live node i (appending its C expression
@@ -745,6 +801,31 @@ class Lowered:
         g = self.g
         seen_checks = set()
         table = getattr(self, "_const_table", None)
+        batch = {}             # division node -> (its group, position in it); set by emit(div_batch=True) only
+        for grp in (getattr(self, "_div_batch", None) or ()):
+            for k, n in enumerate(grp):
+                batch[n] = (grp, k)
+        inv = {}               # division node -> name of the reciprocal of its denominator
+
+        def group_lines(grp, name):
+            """the prefix-product inversion of a group (div_groups), printed at its first division"""
+            den = [name[self.denominator(n)] for n in grp]
+            tag, n = "b%d" % grp[0], len(grp)
+            out, prod = [], den[0]
+            for k in range(1, n):                         # p_k = d_1 .. d_(k+1)
+                out.append("    const real %s_p%d = %s * %s;" % (tag, k, prod, den[k]))
+                prod = "%s_p%d" % (tag, k)
+            out.append("    const real %s_t%d = rmt_rcp(%s);" % (tag, n - 1, prod))
+            for k in range(n - 1, 0, -1):                 # 1/d_(k+1) = t_k p_(k-1),  t_(k-1) = t_k d_(k+1)
+                below = den[0] if k == 1 else "%s_p%d" % (tag, k - 1)
+                out.append("    const real %s_i%d = %s_t%d * %s;" % (tag, k, tag, k, below))
+                if k > 1:
+                    out.append("    const real %s_t%d = %s_t%d * %s;" % (tag, k - 1, tag, k, den[k]))
+                else:
+                    out.append("    const real %s_i0 = %s_t1 * %s;" % (tag, tag, den[1]))
+                inv[grp[k]] = "%s_i%d" % (tag, k)
+            inv[grp[0]] = "%s_i0" % tag
+            return out
 
         def lit(v):
             if math.isnan(v):
@@ -774,6 +855,10 @@ class Lowered:
             A = name[a]
             B = name[b] if (b is not None and op != "powi") else None
             pre = []
+            if i in batch and i not in inv:               # the first division of a group: its reciprocals, all at once
+                if not declare:
+                    raise LoweringError("a batched division inside the cached section")
+                lines.extend(group_lines(batch[i][0], name))
             if op == "add":
                 e = "%s + %s" % (A, B)
             elif op == "sub":
@@ -782,10 +867,10 @@ class Lowered:
                 e = "%s * %s" % (A, B)
             elif op == "div":
                 pre.append("RMT_CHECK_DEN(flag, %s);" % B)
-                e = "rmt_div(%s, %s)" % (A, B)
+                e = "%s * %s" % (A, inv[i]) if i in inv else "rmt_div(%s, %s)" % (A, B)
             elif op == "rcp":
                 pre.append("RMT_CHECK_DEN(flag, %s);" % A)
-                e = "invT" if A == "T" else "rmt_rcp(%s)" % A     # 1/T comes with the node state
+                e = "invT" if A == "T" else (inv[i] if i in inv else "rmt_rcp(%s)" % A)     # 1/T comes with the node state
             elif op == "expn":      # stands for 1/exp(A): Python raises if exp(A) overflows or is 0
                 pre.append("RMT_CHECK_EXP(flag, rmt_abs(%s));" % A)
                 e = "rmt_exp(-%s)" % A
@@ -1052,11 +1137,14 @@ class Lowered:
         return {"roots": roots, "kind": kind, "slot": slot, "fslot": fslot, "slots": nslots, "branch": branch,
                 "prologue": prologue, "tslot": tslot, "outside_exp": outside}
 
-    def emit(self, fname="rmt_kinetics", const_table=False, kcache=False, kcache_gen=True, kcache_thr=None):
+    def emit(self, fname="rmt_kinetics", const_table=False, kcache=False, kcache_gen=True, kcache_thr=None,
+             div_batch=False):
         """The device function of the rates.  ``kcache``: with the cached section of kcache_plan() for callers that
         pass a cache (template parameter KC with KC::enabled; every other caller passes rmt_nocache_t and gets the
-        plain evaluation - the section is discarded at compile time)."""
+        plain evaluation - the section is discarded at compile time).  ``div_batch``: independent divisions share one
+        reciprocal (div_groups; plan.Mechanism.source switches it on unless RMT_DIV_BATCH 0 is among its defines)."""
         self._const_table = {} if const_table else None
+        self._div_batch = self.div_groups() if div_batch else None        # (one reciprocal per group, see div_groups)
         plan = self.kcache_plan(kcache_gen) if kcache else None
         self._kc_thr = self.KC_THR
         if kcache_thr is not None:        # (tests: a smaller range makes the callers' out-of-range handling run)
@@ -1068,6 +1156,7 @@ class Lowered:
         else:
             lines, name = self._emit_cached(plan)
         table, self._const_table = self._const_table, None
+        self._div_batch = None
         body = "\n".join(lines)
         if table:
             vals = sorted(table, key=table.get)

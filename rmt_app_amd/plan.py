@@ -171,6 +171,9 @@ class Mechanism:
             "#define RMT_NPT %d" % npt,
             "#define RMT_LDS_STATE %d" % self.lds_state(fp32, block, npt, lds_state),
             "#define RMT_LDS_STATE_CHAIN %d" % self.lds_state(fp32, block, npt, lds_state, chained=True),
+            # whether the rate expressions read SpCoi at all: where they do not, the node function forms the mole
+            # fractions from the scaled state itself (csrc/kernels/20_node_n2.inc, RMT_NODE_X_FROM_STATE)
+            "#define RMT_KIN_USES_C %d" % (1 if any(self.device_dag().uses("C%d" % i) for i in range(self.S)) else 0),
         ] + ([] if (block > 64 or "RMT_EXP_BITS" in (defines or {})) else [
             # one-wave workgroups (small meshes, big ensembles): the 16 KiB exp table would cap the CU
             # at 9 resident waves (measured -30 % at N=20, E=2048); they keep the 64-entry table
@@ -295,11 +298,22 @@ class Mechanism:
         """Complete translation unit: prelude + template with the lowered kinetics spliced in."""
         if "RMT_KINETICS_SOURCE" not in template:
             raise ValueError("kernel template lacks the RMT_KINETICS_SOURCE marker")
+        # one reciprocal for the independent divisions of the rate laws (lowering.Lowered.div_groups).  RMT_DIV_BATCH is
+        # a switch of this generator, not a macro the kernel source reads: 0 switches the pass off.  Not in a unit that
+        # also prints the gradient DAG (the same two conditions as below): the stiff and the steady steppers take the
+        # rates from rmt_kinetics in one place and from rmt_kinetics_jac / _jacp in another, the same arithmetic in both.
+        # Not in fp32 either: v_rcp_f32 has no Newton step that would turn the reciprocal of an overflowed product into
+        # NaN, it returns 0 and the rates would be finite and wrong - and the range is 1e+-38 there.  The same goes for
+        # the plain 1.0/b of a kernel built with RMT_FAST_MATH 0.
+        with_jac = bool((defines or {}).get("RMT_WITH_ROS4") or (defines or {}).get("RMT_WITH_N1"))
+        batch = str((defines or {}).get("RMT_DIV_BATCH", "1")) != "0" and not with_jac and not fp32 \
+            and str((defines or {}).get("RMT_FAST_MATH", "1")) != "0"
         kin = self.device_dag().emit("rmt_kinetics", const_table=bool((defines or {}).get("RMT_KINETICS_KTAB")),
                                      kcache=(str((defines or {}).get("RMT_KCACHE", "0")) == "1"
                                              or str((defines or {}).get("RMT_KCACHE_CHAIN", "0")) == "1"),
                                      kcache_gen=KCACHE_GEN[str((defines or {}).get("RMT_KCACHE_GEN", "1"))],
-                                     kcache_thr=(defines or {}).get("RMT_KCACHE_THR"))
+                                     kcache_thr=(defines or {}).get("RMT_KCACHE_THR"),
+                                     div_batch=batch)
         if (defines or {}).get("RMT_WITH_ROS4"):
             # the stiff stepper's node Jacobian is analytic: rates AND their partials by T, x_i, C_i
             kin += self.device_dag().gradient().emit_jac("rmt_kinetics_jac")

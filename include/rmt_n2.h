@@ -219,6 +219,36 @@ int rmt_n2_monitor_reduce(rmt_n2_monitor* m, void* hip_stream, const void* y, co
  * device with waves), 1 = one workgroup per row (a few long rows); 0 before any */
 int rmt_n2_monitor_last_rows_per_block(const rmt_n2_monitor* m);
 
+/* Controller (solver-config "control"): a sampled PI controller per member, evaluated on the device between two launches
+ * of a stepper (csrc/control_kernels.inc, a translation unit of its own, independent of any mechanism: compile
+ * rmt_n2_control_source() with rmt_n2_compile and the option -ffp-contract=off - the law is then reproducible bit for bit
+ * on the host - and load it with rmt_n2_control_create on the current device).
+ * rmt_n2_control_update enqueues ONE kernel (rmt_n2_control_update_f64, one wave per member) on the stream of `h`, behind
+ * whatever refreshed the member rows and ahead of the next stepper launch, and does not synchronise.  `h` is the N2 handle
+ * whose DEVICE member rows are written - it must come from a forced code object (RMT_FORCING 1 or 2, fp64) whose rows
+ * carry their tail {t_ref, three slopes, ...} at index `tail_at` (16 + S + the mechanism's own parameters).
+ *   y        DEVICE [E][V][N] doubles, the state at the sample time (E = the handle's members; V and N are arguments: the
+ *            kernel only reads y)
+ *   params   DEVICE [E][8] doubles {Kp, Kp*Ts/Ti (0: P only), u0, lo, hi, selector, species index, 0}; selector 0 = outlet
+ *            temperature, 1 = peak temperature, 2 = outlet mole fraction of the species
+ *   setpoint DEVICE [E] doubles, r(t_k) of this sample
+ *   state    DEVICE [E][3] doubles {I, u, samples taken}, zero before the first sample
+ *   log      DEVICE [E][4] doubles {pv, r, u, saturated (0.0 / 1.0)}: this sample's slice of the caller's log
+ *   field    0 / 1 / 2 = inlet temperature (THETA_IN = (u - Tf)/Tf) / inlet pressure (P0 = u) / medium temperature (TM = u);
+ *            the slope of that field in the row's tail becomes 0
+ *   hold     non-zero: only the held u (state[1]) is written into the rows again (behind a refresh that uploaded whole
+ *            rows); y, setpoint and log may be NULL and nothing else changes; members not sampled yet keep their rows
+ * Law: e = r - pv; I' = I + (Kp*Ts/Ti)*e; v = u0 + Kp*e + I'; u = min(max(v, lo), hi); I = I' only if v == u. */
+const char* rmt_n2_control_source(void);
+typedef struct rmt_n2_control rmt_n2_control;
+int rmt_n2_control_create(const void* code, size_t size, rmt_n2_control** out);
+void rmt_n2_control_destroy(rmt_n2_control* c);
+/* the DEVICE member rows of `h` as they are now ([E][16 + S + n_user_params] doubles into host memory; synchronises the
+ * handle's stream): what the last rmt_n2_set_members* uploaded and rmt_n2_control_update wrote since */
+int rmt_n2_get_members(rmt_n2_handle* h, double* members);
+int rmt_n2_control_update(rmt_n2_control* c, rmt_n2_handle* h, const double* y, int V, int N, const double* params,
+                          const double* setpoint, double* state, double* log, int tail_at, int field, int hold);
+
 const char* rmt_n2_last_error(void);
 int rmt_n2_abi_version(void);
 

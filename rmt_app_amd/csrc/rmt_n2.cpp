@@ -22,6 +22,10 @@ static const char* const k_template =
 static const char* const k_monitor_source =
 #include "monitor_kernels_embed.h"
     ;
+// the controller's translation unit (control_kernels.inc): mechanism-independent, compiled on its own
+static const char* const k_control_source =
+#include "control_kernels_embed.h"
+    ;
 
 static thread_local std::string g_err;
 
@@ -312,6 +316,15 @@ extern "C" int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members)
     ON_DEVICE(h);
     const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
     HIP_OK(hipMemcpyAsync(h->d_members, members, mbytes, hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+extern "C" int rmt_n2_get_members(rmt_n2_handle* h, double* members) {
+    if (!h || !members) return fail("null argument");
+    ON_DEVICE(h);
+    const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
+    HIP_OK(hipMemcpyAsync(members, h->d_members, mbytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -789,3 +802,73 @@ extern "C" int rmt_n2_monitor_reduce(rmt_n2_monitor* m, void* hip_stream, const 
 }
 
 extern "C" int rmt_n2_monitor_last_rows_per_block(const rmt_n2_monitor* m) { return m ? m->last_rows_per_block : 0; }
+
+// ---------------------------------------------------------------------------------------------- controller
+// The sampled PI controller (control_kernels.inc): one kernel between two stepper launches, on the handle's stream.  One
+// wave per member at 256 threads; at most RMT_N2_CONTROL_MAX_GRID workgroups (128 waves), the members beyond them are
+// walked grid-stride - the kernel reads one row of the state per member at most and is latency-bound long before that.
+#define RMT_N2_CONTROL_BLOCK 256
+#define RMT_N2_CONTROL_MAX_GRID 32
+
+struct rmt_n2_control {
+    int device = 0;
+    hipModule_t module = nullptr;
+    hipFunction_t f_update = nullptr;
+};
+
+extern "C" const char* rmt_n2_control_source(void) { return k_control_source; }
+
+extern "C" void rmt_n2_control_destroy(rmt_n2_control* c) {
+    if (!c) return;
+    DeviceGuard guard_(c->device);
+    if (c->module) (void)hipModuleUnload(c->module);
+    delete c;
+}
+
+extern "C" int rmt_n2_control_create(const void* code, size_t size, rmt_n2_control** out) {
+    if (!code || !size || !out) return fail("rmt_n2_control_create: null argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail("no HIP device available: the controller has no CPU fallback");
+    rmt_n2_control* c = new rmt_n2_control();
+    hipError_t e = hipGetDevice(&c->device);
+    if (e == hipSuccess) e = hipModuleLoadData(&c->module, code);
+    if (e == hipSuccess) e = hipModuleGetFunction(&c->f_update, c->module, "rmt_n2_control_update_f64");
+    if (e != hipSuccess) {
+        fail("rmt_n2_control_create: %s", hipGetErrorString(e));
+        rmt_n2_control_destroy(c);
+        return 1;
+    }
+    *out = c;
+    return 0;
+}
+
+extern "C" int rmt_n2_control_update(rmt_n2_control* c, rmt_n2_handle* h, const double* y, int V, int N,
+                                     const double* params, const double* setpoint, double* state, double* log,
+                                     int tail_at, int field, int hold) {
+    if (!c || !h || !state) return fail("rmt_n2_control_update: null argument");
+    if (!hold && (!y || !params || !setpoint || !log)) return fail("rmt_n2_control_update: null argument (update)");
+    if (h->fp32) return fail("rmt_n2_control_update: fp64 handles only");
+    if (h->device != c->device)
+        return fail("rmt_n2_control_update: the handle lives on device %d, the controller on %d", h->device, c->device);
+    const int width = RMT_N2_MEMBER_FIXED + h->S + h->NU;
+    if (tail_at < RMT_N2_MEMBER_FIXED + h->S || tail_at + 4 > width)
+        return fail("rmt_n2_control_update: the rows of this handle (%d doubles) carry no forcing tail at %d", width, tail_at);
+    if (field < 0 || field > 2) return fail("rmt_n2_control_update: field must be 0, 1 or 2 (got %d)", field);
+    if (!hold && (N < 1 || V < h->S || V > h->S + 1))
+        return fail("rmt_n2_control_update: bad sizes V=%d N=%d for S=%d", V, N, h->S);
+    if (((size_t)y | (size_t)params | (size_t)setpoint | (size_t)state | (size_t)log) % sizeof(double))
+        return fail("rmt_n2_control_update: misaligned pointer");
+    ON_DEVICE(h);
+    int E = h->E, S = h->S;
+    const int waves = RMT_N2_CONTROL_BLOCK / 64;
+    int grid = (E + waves - 1) / waves;
+    if (grid > RMT_N2_CONTROL_MAX_GRID) grid = RMT_N2_CONTROL_MAX_GRID;
+    void* args[] = {(void*)&y,   (void*)&h->d_members, (void*)&params, (void*)&setpoint, (void*)&state,
+                    (void*)&log, (void*)&E,            (void*)&S,      (void*)&V,        (void*)&N,
+                    (void*)&width, (void*)&tail_at,    (void*)&field,  (void*)&hold};
+    HIP_OK(hipModuleLaunchKernel(c->f_update, (unsigned)grid, 1, 1, RMT_N2_CONTROL_BLOCK, 1, 1, 0, h->stream, args,
+                                 nullptr));
+    return 0;
+}

@@ -65,6 +65,7 @@ def lib():
     L.rmt_n2_set_mode.argtypes = [vp, C.c_int]
     L.rmt_n2_set_members.argtypes = [vp, C.POINTER(dbl)]
     L.rmt_n2_set_members_async.argtypes = [vp, vp]
+    L.rmt_n2_get_members.argtypes = [vp, C.POINTER(dbl)]
     L.rmt_n2_rhs.argtypes = [vp, dbl, vp, vp]
     L.rmt_n2_rk4.argtypes = [vp, vp, dbl, dbl, i64]
     L.rmt_n2_multistep.argtypes = [vp, vp, dbl, dbl, i64, C.c_int]
@@ -81,6 +82,11 @@ def lib():
     L.rmt_n2_monitor_destroy.restype = None
     L.rmt_n2_monitor_reduce.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.rmt_n2_monitor_last_rows_per_block.argtypes = [vp]
+    L.rmt_n2_control_source.restype = cp
+    L.rmt_n2_control_create.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.rmt_n2_control_destroy.argtypes = [vp]
+    L.rmt_n2_control_destroy.restype = None
+    L.rmt_n2_control_update.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int]
     L.rmt_n2_hiprtc_path.restype = cp
     L.rmt_n2_compile_options.restype = cp
     if L.rmt_n2_abi_version() != ABI_VERSION:
@@ -135,6 +141,52 @@ class Monitor:
         if getattr(self, "m", None):
             lib().rmt_n2_monitor_destroy(self.m)
             self.m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CONTROL_OPTS = "-ffp-contract=off"       # the control law: one rounded fp64 operation each, reproducible in numpy
+
+
+def control_source():
+    """The controller's translation unit (csrc/control_kernels.inc, embedded in the library next to the template)."""
+    return lib().rmt_n2_control_source().decode()
+
+
+def control_code(arch="gfx950"):
+    """Code object of the control kernel from the in-tree cache (compiled on first use, with floating-point contraction
+    off; works without a GPU)."""
+    import hashlib
+    src = control_source()
+    return compile_cached(src, "control-" + hashlib.sha256(src.encode()).hexdigest()[:24], arch, CONTROL_OPTS)
+
+
+class Control:
+    """rmt_n2_control on the current device: the sampled PI controller's kernel (include/rmt_n2.h).  Independent of any
+    mechanism; ``update`` enqueues one kernel on the stream of the N2 handle whose device rows it writes."""
+
+    def __init__(self, arch="gfx950", code=None):
+        code = control_code(arch) if code is None else code
+        self._code = C.create_string_buffer(code, len(code))
+        c = C.c_void_p()
+        check(lib().rmt_n2_control_create(C.cast(self._code, C.c_void_p), len(code), C.byref(c)))
+        self.c = c
+
+    def update(self, handle, y_ptr, V, N, params_ptr, setpoint_ptr, state_ptr, log_ptr, tail_at, field, hold=False):
+        """Enqueue an update (or, with ``hold``, the rewrite of the held value); nothing is synchronised."""
+        def ptr(p):
+            return C.c_void_p(p) if p else None
+        check(lib().rmt_n2_control_update(self.c, handle, ptr(y_ptr), int(V), int(N), ptr(params_ptr), ptr(setpoint_ptr),
+                                          ptr(state_ptr), ptr(log_ptr), int(tail_at), int(field), int(bool(hold))))
+
+    def close(self):
+        if getattr(self, "c", None):
+            lib().rmt_n2_control_destroy(self.c)
+            self.c = None
 
     def __del__(self):
         try:

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from . import hipbind, monitor, plan, schedule
+from . import control, hipbind, monitor, plan, schedule
 from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
@@ -470,6 +470,13 @@ class N2Device:
         hipbind.check(hipbind.lib().rmt_n2_set_members_async(self.h, C.c_void_p(pinned.data_ptr())))
         return pinned
 
+    def get_members(self):
+        """The device rows as they are now [E][row_width] (synchronises the stream): what the last refresh uploaded and
+        the controller's kernel wrote since."""
+        out = np.zeros((self.E, self.row_width))
+        hipbind.check(hipbind.lib().rmt_n2_get_members(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
     def set_mode(self, mode):
         hipbind.check(hipbind.lib().rmt_n2_set_mode(self.h, {"auto": 0, "reg": 1, "mem": 2, "chain": 3}[mode]))
 
@@ -503,6 +510,20 @@ class N2Device:
         #                                                 caching allocator hands memory out in stream order)
         self._mon.reduce(self._stream, y.data_ptr(), dydt.data_ptr() if residual else 0, self.E, self.mech.V, self.N,
                          self.fp32, out.data_ptr())
+
+    def control(self, y, loop, k=None):
+        """Queue the controller's kernel on the device's stream, behind the refresh of the member rows and ahead of the
+        next stepper launch (csrc/control_kernels.inc): sample ``k`` of the ControlLoop - measure on the state y, evaluate
+        the law, write slice k of the log and the manipulated field of this device's rows - or, with k = None, only
+        write the held value into the rows again.  Nothing is copied or synchronised."""
+        if not self.forced or self.fp32:
+            raise hipbind.RmtN2Error("the controller writes the rows of a forced fp64 code object (RMT_FORCING 1 or 2)")
+        if k is not None:
+            self._chk_state(y)
+        assert loop.E == self.E
+        loop.kernel.update(self.h, y.data_ptr() if k is not None else 0, self.mech.V, self.N, loop.params.data_ptr(),
+                           loop.setpoints[k].data_ptr() if k is not None else 0, loop.state.data_ptr(),
+                           loop.log[k].data_ptr() if k is not None else 0, self.mech.row_width, loop.field, k is None)
 
     def to_device(self, y):
         t = self.torch.as_tensor(np.ascontiguousarray(y), dtype=self.dtype)
@@ -632,6 +653,8 @@ class AutoStepper:
             self._dr = self._dr()
             if getattr(self, "_rows", None) is not None:
                 self._dr.set_members(self._rows)
+            if getattr(self, "_loop", None) is not None:      # (its rows came from the host: the held value again)
+                self._dr.control(None, self._loop)
         return self._dr
 
     def set_members(self, rows):
@@ -654,6 +677,14 @@ class AutoStepper:
 
     def monitor(self, y, out, residual=False):
         self.last.monitor(y, out, residual)
+
+    def control(self, y, loop, k=None):
+        """the controller's kernel for both devices: the explicit one takes the sample, the stiff one - once it exists -
+        has the held value written into its own rows"""
+        self._loop = loop
+        self.d45.control(y, loop, k)
+        if not callable(self._dr):
+            self._dr.control(y, loop, None)
 
     def raise_on_flags(self):
         self.last.raise_on_flags()
@@ -979,11 +1010,43 @@ class Forcing:
         return None
 
 
+class ControlLoop:
+    """The device side of one run's controllers (control.Control): the kernel's module and its buffers - parameter blocks
+    [E][8], setpoints [K][E], controller state [E][3] and the log [K][E][4], which comes back once, at the end."""
+
+    def __init__(self, ctl, dev):
+        d = getattr(dev, "d45", dev)                  # ("hip-auto": both devices live on the same GPU)
+        torch = d.torch
+        self.ctl, self.E, self.field = ctl, ctl.E, ctl.field
+        arch = torch.cuda.get_device_properties(d.device).gcnArchName.split(":")[0]
+        with torch.cuda.device(d.device):
+            self.kernel = hipbind.Control(arch)
+        self.params = torch.from_numpy(ctl.params()).to(d.device)
+        self.setpoints = torch.from_numpy(np.ascontiguousarray(ctl.setpoints)).to(d.device)
+        self.state = torch.zeros((ctl.E, control.STATE), dtype=torch.float64, device=d.device)
+        self.log = torch.zeros((ctl.K, ctl.E, control.LOG), dtype=torch.float64, device=d.device)
+        self.taken = 0
+
+    def close(self):
+        self.kernel.close()
+
+
+def launch_list(opTSpan, forcing=None, mon=None, ctl=None):
+    """The launches of a run [(t0, t1, index of the output time the launch ends at or None, index of the monitor sample it
+    ends at or None, index of the control sample taken at its start or None)]: the sorted union of output times, schedule
+    breakpoints, monitor samples and control samples."""
+    tNo = len(opTSpan) - 1
+    launches = forcing.launches if forcing is not None else \
+        [(float(opTSpan[i]), float(opTSpan[i + 1]), i + 1) for i in range(tNo)]
+    launches = mon.refine(launches, float(opTSpan[-1])) if mon is not None else [l + (None,) for l in launches]
+    return ctl.refine(launches, float(opTSpan[-1])) if ctl is not None else [l + (None,) for l in launches]
+
+
 PIPELINE_BYTES = 1 << 30       # pinned host memory one batch of queued output intervals may hold (integrate_intervals)
 
 
 def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_interval, sync=None, outlet=False,
-                        forcing=None, mon=None):
+                        forcing=None, mon=None, ctl=None):
     """The reference's time loop (pbHomoReactor.py:3589-3690, pbReactor.py:711-762): one device
     launch per output interval; ``on_interval(i, t1, Y_host)`` packs the end state ([E][V*zNo], or [E][V] = the
     outlet node with ``outlet``).  With ``sync`` (multi-rank ensemble) a failure on any rank is raised on every
@@ -994,14 +1057,16 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     that ends at sample k the row reductions of the state are queued into slice k of ONE device buffer [K][E][V][5]
     (sample 0 before the first launch; with "residual" behind rmt_n2_rhs at that state).  Nothing is copied or
     synchronised per sample: the buffer comes back once, at the end, as ``stats["monitor-raw"]`` ([K][E_local][V][5];
-    the callers pop it).  A run that raises on flags returns no monitor."""
+    the callers pop it).  A run that raises on flags returns no monitor.
+    ``ctl`` (a control.Control, solver-config "control"; needs ``forcing``): the walk is split at the control samples too.
+    The order in the stream for every launch is: refresh of the rows, the controller's kernel, the stepper - the update
+    when the launch starts at a sample time, else (once a sample has been taken) the rewrite of the held value, because
+    the refresh uploads whole rows.  The log [K][E_local][4] comes back once, as ``stats["control-raw"]``."""
     import torch
     tNo = len(opTSpan) - 1
-    # (t0, t1, index of the output time the launch ends at or None, index of the sample it ends at or None)
-    launches = forcing.launches if forcing is not None else \
-        [(float(opTSpan[i]), float(opTSpan[i + 1]), i + 1) for i in range(tNo)]
-    launches = mon.refine(launches, float(opTSpan[-1])) if mon is not None else [l + (None,) for l in launches]
+    launches = launch_list(opTSpan, forcing, mon, ctl)
     nL = len(launches)
+    loop = ControlLoop(ctl, dev) if ctl is not None else None
     mbuf = None
     if mon is not None:
         mbuf = torch.zeros((mon.K, y.shape[0], y.shape[1]//zNo, monitor.SLOTS), dtype=torch.float64, device=y.device)
@@ -1010,7 +1075,7 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
         if mbuf is not None and k is not None:
             dev.monitor(y, mbuf[k], mon.residual)
     stats = {"steps": 0, "rhs_evals": 0, "node_steps": 0, "accepted": None, "rejected": None}
-    if mon is not None:
+    if mon is not None or ctl is not None:
         stats["launches"] = nL
     adaptive = ivp in ("hip-rk45", "hip-ros4", "hip-auto")
 
@@ -1059,10 +1124,13 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     def queue(lo, hi):
         staged = []
         for i in range(lo, hi):
-            t0, t1, kout, ksample = launches[i]
+            t0, t1, kout, ksample, kctl = launches[i]
             _progress(i + 1, nL + 1, quiet)
             # (the page-locked rows of a queued refresh stay alive until the batch has landed)
             rows = forcing.refresh(dev, t0, t1, queued) if forcing is not None else None
+            if loop is not None and (kctl is not None or loop.taken):
+                dev.control(y, loop, kctl)                       # behind the refresh, ahead of the stepper
+                loop.taken += kctl is not None
             step(i, t0, t1)
             sample(ksample)                                      # queued right behind its launch, into slice ksample
             state = counters = landed = None
@@ -1080,22 +1148,28 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
 
     _progress(0, tNo + 1, quiet)
     guarded(sync, sample, 0)
-    for lo in range(0, nL, batch):
-        for kout, state, counters, landed, _ in guarded(sync, queue, lo, min(nL, lo + batch)):
-            if landed is not None:                                # packing launch i while the device is at i+1, i+2, ...
-                landed.synchronize()
-            if counters is not None:
-                acc, rej = step_counts(counters.numpy())
-                stats["accepted"] = acc if stats["accepted"] is None else stats["accepted"] + acc
-                stats["rejected"] = rej if stats["rejected"] is None else stats["rejected"] + rej
-            if kout is not None:                                  # (None: a breakpoint or a sample time - nothing to pack)
-                on_interval(kout - 1, float(opTSpan[kout]), state.numpy().astype(np.float64))
-        if sync is None:
-            dev.raise_on_flags()                                  # (sticky status words: whatever a launch of the batch flagged)
-    if ivp == "hip-auto":
-        stats["method-per-interval"] = list(dev.choices)
-    if mbuf is not None:
-        stats["monitor-raw"] = mbuf.cpu().numpy()                 # the ONE copy of the monitor buffer
+    try:
+        for lo in range(0, nL, batch):
+            for kout, state, counters, landed, _ in guarded(sync, queue, lo, min(nL, lo + batch)):
+                if landed is not None:                                # packing launch i while the device is at i+1, i+2, ...
+                    landed.synchronize()
+                if counters is not None:
+                    acc, rej = step_counts(counters.numpy())
+                    stats["accepted"] = acc if stats["accepted"] is None else stats["accepted"] + acc
+                    stats["rejected"] = rej if stats["rejected"] is None else stats["rejected"] + rej
+                if kout is not None:                                  # (None: a breakpoint or a sample time - nothing to pack)
+                    on_interval(kout - 1, float(opTSpan[kout]), state.numpy().astype(np.float64))
+            if sync is None:
+                dev.raise_on_flags()                                  # (sticky status words: whatever a launch of the batch flagged)
+        if ivp == "hip-auto":
+            stats["method-per-interval"] = list(dev.choices)
+        if mbuf is not None:
+            stats["monitor-raw"] = mbuf.cpu().numpy()                 # the ONE copy of the monitor buffer
+        if loop is not None:
+            stats["control-raw"] = loop.log.cpu().numpy()            # the ONE copy of the controllers' log
+    finally:
+        if loop is not None:
+            loop.close()
     if sync is not None:
         stats = gather_stats(stats, sync, ivp, nL, zNo, dev.jacobian_evals)
     else:
@@ -1185,17 +1259,24 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
     block, npt = cfg.get('block'), cfg.get('nodes-per-thread')
     # "schedule": time-varying inlet / coolant conditions (schedule.py); absent = None = exactly the run without it
     sched = schedule.parse(modelInput, members_inputs, ivp) if with_schedule else None
+    # "control": a sampled PI controller per member on the device (control.py); absent = None = exactly the run without it.
+    # A controlled run is a forced run: without a "schedule" it gets a constant one of every member's own values.
+    control.check_model(modelInput)
+    ctl, forced_by = control.parse(modelInput, members_inputs, ivp, sched, sync is not None) if with_schedule \
+        else (None, sched)
+    if ctl is not None:
+        ctl.check_budget(PIPELINE_BYTES)
     # "monitor": time series between the output times (monitor.py); absent = None = exactly the run without it
     mon = monitor.parse(modelInput, tNo)
     if mon is not None:
         mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
     forcing = None
-    if sched is not None:
+    if forced_by is not None:
         if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
             raise NotImplementedError("solver-config 'schedule' with the stiff stepper needs a mechanism of at most 8 "
                                       "variables per node (this one has %d): its four-lane form does not carry the "
                                       "forcing - use ivp 'hip-rk45' or 'hip-rk4'" % mech.V)
-        forcing = Forcing(sched if sync is None else sched.members(sync.lo, sync.hi), opT, tNo, zNo,
+        forcing = Forcing(forced_by if sync is None else forced_by.members(sync.lo, sync.hi), opT, tNo, zNo,
                           cfg.get('device-mode'))
         if ivp == "hip-rk4" and block is None:
             # the geometry of ONE workgroup per reactor (no chunks: the chained kernels do not carry the forcing)
@@ -1228,7 +1309,8 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
                 for e, pk in enumerate(pack_all(Yg, named, mech, 1 if outlet else zNo, t1)):
                     packs[e].append(pk)
         stats = integrate_intervals(dev, y, cfg, ivp, opTSpan, len(named_local), zNo, quiet or not packer, on_interval,
-                                    sync, outlet, forcing, mon)
+                                    sync, outlet, forcing, mon, ctl)
+        logs = stats.pop("control-raw", None)                          # [K][E][4]
         monitors = attach_monitor(stats, mon, sync, lambda e, raw: monitor.result_entry(
             raw, mon.times, mech, zNo, named[e], model, inputs[e]['reactor']['ReLe'], mon.residual))
         if forcing is not None:
@@ -1247,6 +1329,12 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
     if members_inputs:
         # multi-rank: rank 0 holds the whole sweep, the other ranks None (and an empty dataPack)
         res["ensemble"] = [result(p, mi, zNo, opTSpan) for p, mi in zip(packs, inputs)] if packer else None
+    if ctl is not None:
+        entries = [ctl.result_entry(logs[:, e]) for e in range(logs.shape[1])]
+        res["control"] = entries[0]
+        if members_inputs:
+            for entry, c in zip(res["ensemble"], entries):
+                entry["control"] = c
     if monitors:
         res["monitor"] = monitors[0]
         if members_inputs:

@@ -32,6 +32,8 @@ def rmtExe(modelInput):
                              "model 'N2' (got model %r)" % (modelType,))
         from .monitor import check_model
         check_model(modelInput)               # solver-config 'monitor': models N2 and M2 only
+        from .control import check_model as check_control
+        check_control(modelInput)             # solver-config 'control': model N2 only
         if modelType == "N2":
             from .n2 import run_n2
             ensemble = modelInput['solver-config'].get('ensemble')

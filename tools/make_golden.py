@@ -5,9 +5,10 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
-coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14).
+coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
+closed-loop runs with the sampled PI controller, G15).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
 """
@@ -982,6 +983,235 @@ def g_feed(which=None):
         print("G14 %s written (%.0f s)" % (name, time.time() - t0))
 
 
+# --------------------------------------------------------------------------- G15
+# Closed-loop runs (solver-config "control", rmt_app_amd/control.py): a sampled PI controller moves the inlet pressure.
+# SciPy on the oracle's RHS with pr["T0"], pr["P0"], pr["Tm"] (and pr["SpCoi0"]) set per call, restarted at every sample
+# time and breakpoint; the control law, the sample times and the setpoint are restated here - nothing of the product is
+# imported.  The cases are written to g15_control.json; each .npz holds the states at the output times and the log
+# (t_k, pv_k, r_k, u_k, saturated).
+G15_SP_STEP = {"time": [0.0, 0.25, 0.25, 0.4], "value": [621.0, 621.0, 620.0, 620.0]}
+G15_PI = {"measured": "outlet-temperature", "manipulated": "inlet-pressure", "setpoint": G15_SP_STEP, "sample-time": 0.01,
+          "start": 0.1, "gain": 5.0e4, "integral-time": 0.05, "limits": [4.0e6, 6.0e6]}
+G15_CASES = {
+    "CA": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 4,
+           "schedule": {"time": [0.0, 0.2, 0.2, 0.4], "medium-temperature": [523.0, 523.0, 533.0, 533.0]},
+           "control": dict(G15_PI)},
+    "CB": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 4,
+           "schedule": {"time": [0.0, 0.2, 0.2, 0.4], "medium-temperature": [523.0, 523.0, 533.0, 533.0]},
+           # (setpoint 622.2 -> 621.2 instead of CA's 621 -> 620: with CA's the output sat at the lower limit for the whole run
+           # and the rerun at rtol 1e-12 missed the 1e-9 condition; with 622.5 -> 621.5 only two samples saturated,
+           # profiles/control.md)
+           "control": dict(G15_PI, limits=[4.95e6, 5.05e6],
+                           setpoint={"time": [0.0, 0.25, 0.25, 0.4], "value": [622.2, 622.2, 621.2, 621.2]})},
+    # (in the first 0.06 s the bed heats up from the feed temperature and the hottest node is the outlet: the setpoint ramp
+    # runs a few K ahead of the open-loop peak, 524.5 K at t = 0.01 .. 564.5 K at t = 0.05)
+    "CC": {"input": "dme_nb", "zNo": 600, "period": 0.06, "tNo": 3, "method": "DOP853",
+           "schedule": {"time": [0.0, 0.02, 0.04, 0.06], "medium-temperature": [523.0, 523.0, 531.0, 531.0],
+                        "inlet-concentration": [G14_FEED, G14_FEED, G14_NEW, G14_NEW]},
+           "control": {"measured": "peak-temperature", "manipulated": "inlet-pressure",
+                       "setpoint": {"time": [0.0, 0.06], "value": [520.0, 580.0]}, "sample-time": 0.01, "start": 0.01,
+                       "gain": 5.0e4, "integral-time": 0.05, "limits": [4.0e6, 6.0e6]}},
+    # (the gain is filled in by g15_cd_gain: half the inverse of the generator's own open-loop step response)
+    "CD": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2, "members": [0, 3],
+           "ensemble": {"temperature": [518.0, 528.0], "pressure": [4.8e6, 5.2e6]},
+           "control": {"measured": {"outlet-mole-fraction": "DME"}, "manipulated": "inlet-pressure", "setpoint": 0.0150,
+                       "sample-time": 0.02, "start": 0.1, "gain": None, "integral-time": 0.05, "limits": [4.0e6, 6.0e6]}},
+}
+G15_SHELL = ["H2", "CO2", "H2O", "CO", "CH3OH", "DME"]       # dme_nb's shell components
+G15_LOOSEST_BOUND = 1e-6                                     # the loosest bound of tests/test_gpu_control.py
+
+
+def _g15_setpoint(sp, t, tol):
+    if not isinstance(sp, dict):
+        return float(sp)
+    T, v = np.asarray(sp["time"], dtype=float), np.asarray(sp["value"], dtype=float)
+    j = int(np.argmin(np.abs(T - t)))
+    if abs(T[j] - t) <= tol:
+        t = float(T[j])
+    k = int(np.searchsorted(T, t, side="right")) - 1
+    if k >= len(T) - 1:
+        return float(v[-1])
+    return float(v[k] + (v[k + 1] - v[k])*(t - T[k])/(T[k + 1] - T[k]))
+
+
+def _g15_measure(ctl, y, S, N, Tf):
+    Y = np.asarray(y, dtype=float).reshape(S + 1, N)
+    m = ctl["measured"]
+    if m == "outlet-temperature":
+        return float(Y[S, N - 1]*Tf + Tf)
+    if m == "peak-temperature":
+        return float(np.max(Y[S])*Tf + Tf)
+    s = G15_SHELL.index(m["outlet-mole-fraction"])
+    tot = 0.0
+    for i in range(S):
+        tot += float(Y[i, N - 1])
+    return float(Y[s, N - 1])/tot
+
+
+def g15_trajectory(case, member=None, rtol=1e-10, atol=1e-13, gain=None, step=None, t_stop=None, quiet_run=False):
+    """Closed loop: whole states at the output times and the log [K][5] = (t_k, pv_k, r_k, u_k, saturated).
+    ``gain``: replaces the case's (0.0: the open loop on the same restarts); ``step`` = (t_s, dP): no controller, the inlet
+    pressure steps by dP at sample time t_s (the open-loop step response); ``t_stop``: stop there."""
+    from oracle import n2_oracle as O
+    mi = _g13_member_input(case, member)
+    pr = dict(O.setup_n2(mi, zNo=case["zNo"]))
+    f = O.make_rhs_vec(pr)
+    S, N, Tf = pr["compNo"], case["zNo"], float(pr["Tf"])
+    sch = case.get("schedule") or {"time": [0.0]}
+    ctl = case["control"]
+    assert ctl["manipulated"] == "inlet-pressure"
+    own = {"T0": pr["T0"], "P0": pr["P0"], "Tm": pr["Tm"], "SpCoi0": np.array(pr["SpCoi0"], dtype=float)}
+    vals = {}
+    for key, name in G13_KEYS + (("inlet-concentration", "SpCoi0"),):
+        if sch.get(key) is not None:
+            vals[name] = np.asarray(sch[key], dtype=float)
+    assert "P0" not in vals
+    if "SpCoi0" in vals:
+        assert np.all(np.max(vals["SpCoi0"], axis=1) == float(np.max(own["SpCoi0"])))
+    period = float(case["period"])
+    tol = 1e-12*period
+    out_t = np.linspace(0.0, period, case["tNo"] + 1)
+    marks = sorted(set(out_t.tolist()) | {b for b in sch["time"] if 0 < b < period and np.min(np.abs(out_t - b)) > tol})
+    Ts, start = float(ctl["sample-time"]), float(ctl.get("start", 0.0))
+    samples, k = [], 0
+    while start + k*Ts < period - tol:
+        t = start + k*Ts
+        j = int(np.argmin(np.abs(np.array(marks) - t)))
+        samples.append(marks[j] if abs(marks[j] - t) <= tol else t)      # a sample at a mark IS that mark
+        k += 1
+    marks = sorted(set(marks) | set(samples))
+    Kp = float((ctl["gain"] or 0.0) if gain is None else gain)      # (None: case CD before g15_cd_gain, step runs only)
+    Ti = ctl.get("integral-time")
+    Ki = 0.0 if Ti is None else Kp*Ts/float(Ti)
+    lo, hi = (float(x) for x in ctl["limits"])
+    u0 = float(own["P0"])
+    I, u = 0.0, u0
+    y = np.array(pr["IV"], dtype=float)
+    states, log = [], []
+    method = case.get("method", "LSODA")
+    for a, b in zip(marks[:-1], marks[1:]):
+        if t_stop is not None and a >= t_stop - tol:
+            break
+        if a in samples:
+            pv = _g15_measure(ctl, y, S, N, Tf)
+            r = _g15_setpoint(ctl["setpoint"], a, tol)
+            if step is None:
+                # the law: one rounded fp64 operation each, in this order
+                e = r - pv
+                Ip = I + Ki*e if Ki != 0.0 else I
+                v = (u0 + Kp*e) + Ip
+                u = lo if v < lo else v
+                u = hi if u > hi else u
+                if v == u:
+                    I = Ip
+                log.append([a, pv, r, u, float(v != u)])
+            else:
+                if abs(a - step[0]) <= tol:
+                    u = u0 + step[1]
+                log.append([a, pv, r, u, 0.0])
+        piece = {name: _pwv_piece(sch["time"], v, a, b) for name, v in vals.items()}
+        pr["P0"] = u
+
+        def ft(t, yy, piece=piece, a=a):
+            for name, (v0, s) in piece.items():
+                pr[name] = v0 + s*(t - a)
+            return f(t, yy)
+        t0 = time.time()
+        sol = REAL_SOLVE_IVP(ft, (a, b), y, method=method, rtol=rtol, atol=atol)
+        if not sol.success:
+            raise RuntimeError(sol.message)
+        y = sol.y[:, -1]
+        if not quiet_run:
+            print("G15 %s%s: (%.4f, %.4f) u=%.6e nfev=%d %.0f s" % (
+                case.get("name", ""), "" if member is None else " member %d" % member, a, b, u, sol.nfev,
+                time.time() - t0), flush=True)
+        if np.min(np.abs(out_t - b)) <= tol:
+            states.append(y.copy())
+    return out_t[1:len(states) + 1], np.array(states), np.array(log)
+
+
+def _g15_state_difference(A, B, S, Tf):
+    """max over nodes and output times of |d mole fraction| and |dT|/T between two sets of states [K][V*N]"""
+    d = 0.0
+    for a, b in zip(A, B):
+        a, b = a.reshape(S + 1, -1), b.reshape(S + 1, -1)
+        xa, xb = a[:S]/np.sum(a[:S], axis=0), b[:S]/np.sum(b[:S], axis=0)
+        Ta, Tb = a[S]*Tf + Tf, b[S]*Tf + Tf
+        d = max(d, float(np.max(np.abs(xa - xb))), float(np.max(np.abs(Ta - Tb)/Tb)))
+    return d
+
+
+def g15_cd_gain():
+    """Case CD's gain from the open-loop step of member 0: the inlet pressure steps by +1e5 Pa at the first sample time,
+    the outlet mole fraction of DME one sample later against the run without the step; Kp = 0.5/(dx/dP), two digits."""
+    case = dict(G15_CASES["CD"], name="CD-step")
+    ctl = case["control"]
+    t1 = ctl["start"] + ctl["sample-time"]
+    _, _, with_step = g15_trajectory(case, 0, step=(ctl["start"], 1.0e5), t_stop=t1 + ctl["sample-time"], quiet_run=True)
+    _, _, without = g15_trajectory(case, 0, step=(ctl["start"], 0.0), t_stop=t1 + ctl["sample-time"], quiet_run=True)
+    dx = with_step[1, 1] - without[1, 1]
+    g = dx/1.0e5
+    Kp = float("%.1e" % (0.5/g))
+    print("G15 CD open-loop step: x_DME %.9e -> %.9e one sample after +1e5 Pa: dx/dP = %.4e 1/Pa, gain = %.1e Pa"
+          % (without[1, 1], with_step[1, 1], g, Kp))
+    return Kp
+
+
+def g15_case(name):
+    case = dict(G15_CASES[name], name=name)
+    case["control"] = dict(case["control"])
+    if case["control"]["gain"] is None:
+        case["control"]["gain"] = g15_cd_gain()
+    return case
+
+
+def g_control(which=None):
+    """``control`` writes the case file and every case; ``control=json`` the case file alone, ``control=<case>`` one case."""
+    if which in (None, "json"):
+        cases = {n: {k: v for k, v in g15_case(n).items() if k != "name"} for n in G15_CASES}
+        with open(os.path.join(GOLD, "g15_control.json"), "w") as f:
+            json.dump({"cases": cases, "rtol": 1e-10, "atol": 1e-13,
+                       "reference": "SciPy LSODA (case CC: DOP853) on oracle.n2_oracle.make_rhs_vec, restarted at every "
+                                    "sample time and breakpoint; the control law restated in tools/make_golden.py"},
+                      f, indent=1)
+        if which == "json":
+            return
+    for name in ([which] if which else list(G15_CASES)):
+        case = g15_case(name)
+        ctl = case["control"]
+        lo, hi = ctl["limits"]
+        S = 6
+        out = {}
+        t0 = time.time()
+        for m in case.get("members", [None]):
+            tag = "" if m is None else "_%d" % m
+            times, states, log = g15_trajectory(case, m)
+            Tf = float(_g13_member_input(case, m)["operating-conditions"]["temperature"])
+            u, sat = log[:, 3], log[:, 4] != 0
+            print("G15 %s%s: u in [%.6e, %.6e], moves by %.4e Pa, %d of %d samples saturated, pv %.6f .. %.6f" % (
+                name, tag, u.min(), u.max(), u.max() - u.min(), int(sat.sum()), len(u), log[:, 1].min(), log[:, 1].max()))
+            if name == "CA":
+                assert not sat.any() and u.min() > lo and u.max() < hi, "CA: u touches a limit"
+                assert u.max() - u.min() >= 1.0e4, "CA: u moves by less than 1e4 Pa"
+            if name == "CB":
+                assert int(sat.sum()) >= 3, "CB: fewer than three saturated samples"
+            _, open_states, _ = g15_trajectory(case, m, gain=0.0, quiet_run=True)
+            d_open = _g15_state_difference(states, open_states, S, Tf)
+            print("G15 %s%s: closed loop against gain = 0: %.4e (needs >= %.1e)" % (name, tag, d_open, 100*G15_LOOSEST_BOUND))
+            assert d_open >= 100*G15_LOOSEST_BOUND, "the closed loop does not differ enough from the open loop"
+            _, tight, tlog = g15_trajectory(case, m, rtol=1e-12, atol=1e-15, quiet_run=True)
+            # relative in the solver's own error weight: |dy| / (|y| + atol/rtol) - a component far below atol/rtol = 1e-3
+            # is held to the absolute tolerance only, its own relative change says nothing about convergence
+            d_tol = float(np.max(np.abs(tight - states)/(np.abs(states) + 1e-13/1e-10)))
+            d_abs = _g15_state_difference(states, tight, S, Tf)
+            print("G15 %s%s: rerun at rtol 1e-12: relative %.4e, in the tests' measure %.4e, u %.4e relative" % (
+                name, tag, d_tol, d_abs, float(np.max(np.abs(tlog[:, 3] - u)/u))))
+            assert d_tol < 1e-9, "the golden states are not converged to 1e-9 relative"
+            out["states" + tag], out["log" + tag] = states, log
+        np.savez_compressed(os.path.join(GOLD, "g15_control_%s.npz" % name), times=times, wall_s=time.time() - t0, **out)
+        print("G15 %s written (%.0f s)" % (name, time.time() - t0))
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1013,6 +1243,8 @@ def main(argv):
             g_schedule(what.split("=", 1)[1] if "=" in what else None)
         elif what == "feed" or what.startswith("feed="):
             g_feed(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "control" or what.startswith("control="):
+            g_control(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

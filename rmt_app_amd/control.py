@@ -27,7 +27,7 @@
 * "control" combines with "schedule" - the schedule moves the disturbances, the controller its own quantity; a schedule
   that also gives the manipulated key is refused.  A run without "schedule" uses a constant schedule of the member's own
   values: a controlled run always loads a forced code object (csrc/kernels/11_forcing.inc).
-* The integration is split at the sample times as "monitor" splits it at its samples; a sample time within
+* The integration is split at the sample times as "monitor" splits it at its samples (launches.merge); a sample time within
   schedule.MERGE_TOL * period of an output time, a breakpoint or a monitor sample IS that time.
 * Ensembles: every member runs its own loop with its own u0, I and Tf; a member may override "gain", "integral-time",
   "setpoint" and "limits" in its own solver-config.control; the times come from the base input.
@@ -35,7 +35,7 @@
   law and writes the manipulated field of the member's device row; the log [K][E][{pv, r, u, saturated}] comes back once,
   at the end of the run, as resModel["control"] = {"time", "measured", "setpoint", "output", "saturated"}.
 
-Host side only (numpy): parsing and validation, the sample times, the refined launch list, the parameter blocks of the
+Host side only (numpy): parsing and validation, the sample times, the parameter blocks of the
 kernel and ``emulate`` - the law in numpy.
 """
 import numpy as np
@@ -154,26 +154,6 @@ class Control:
         out[:, P_LO], out[:, P_HI] = self.lo, self.hi
         out[:, P_SELECT], out[:, P_SPECIES] = float(self.select), float(self.species)
         return out
-
-    def refine(self, launches, period):
-        """Launch list [(t0, t1, k_out, k_sample, k_control)] from a list [(t0, t1, k_out, k_sample)] that covers
-        [0, period] (monitor.Monitor.refine, or the plain list with k_sample = None): split at every control sample that is
-        not yet a mark; k_control = index of the control sample taken at the START of the launch, None when there is none.
-        A sample within MERGE_TOL * period of a mark is that mark."""
-        tol = MERGE_TOL*float(period)
-        marks = [[float(launches[0][0]), None, None, None]] + [[float(l[1]), l[2], l[3], None] for l in launches]
-        at = np.array([m[0] for m in marks])
-        extra = []
-        for kc, t in enumerate(self.times):
-            j = int(np.argmin(np.abs(at - t)))
-            if abs(at[j] - t) <= tol:
-                marks[j][3] = kc
-                self.times[kc] = at[j]
-            else:
-                extra.append([float(t), None, None, kc])
-        marks = sorted(marks + extra, key=lambda m: m[0])
-        return [(marks[i][0], marks[i + 1][0], marks[i + 1][1], marks[i + 1][2], marks[i][3])
-                for i in range(len(marks) - 1)]
 
     def result_entry(self, raw):
         """resModel["control"] of ONE member from its log [K][4]"""

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -87,6 +88,10 @@ struct rmt_n2_handle {
     bool timed = false;
     int last_chunks = 1, last_teams = 0;     // geometry of the last stepper launch (rmt_n2_last_geometry)
 };
+
+// bytes of the member rows [E][RMT_N2_MEMBER_FIXED + S + NU] and of one state [E][V][N]
+static size_t member_bytes(const rmt_n2_handle* h) { return (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double); }
+static size_t state_bytes(const rmt_n2_handle* h) { return (size_t)h->E * h->V * h->N * h->real_size; }
 
 // Every entry point runs on the device the handle was created on: workspace allocations, event
 // records and module launches all act on the CURRENT device, which the caller may have changed
@@ -224,32 +229,36 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
     } while (0)
     CREATE_OK(hipGetDevice(&h->device));
     CREATE_OK(hipModuleLoadData(&h->module, p->code_object));
-    CREATE_OK(hipModuleGetFunction(&h->f_rhs, h->module, "rmt_n2_rhs"));
-    CREATE_OK(hipModuleGetFunction(&h->f_rk4_reg, h->module, "rmt_n2_rk4_reg"));
-    CREATE_OK(hipModuleGetFunction(&h->f_rk4_mem, h->module, "rmt_n2_rk4_mem"));
-    // code objects whose on-chip RK4 stepper caches the temperature-only rate constants (RMT_KCACHE) carry the plain
-    // stepper as a second kernel: it re-integrates the reactors the cached one gave up on
-    if (hipModuleGetFunction(&h->f_rk4_redo, h->module, "rmt_n2_rk4_reg_redo") != hipSuccess)
-        h->f_rk4_redo = nullptr;
-    if (hipModuleGetFunction(&h->f_rk45_reg, h->module, "rmt_n2_rk45_reg") != hipSuccess)
-        h->f_rk45_reg = nullptr;
-    if (hipModuleGetFunction(&h->f_rk45_mem, h->module, "rmt_n2_rk45_mem") != hipSuccess)
-        h->f_rk45_mem = nullptr;
-    if (hipModuleGetFunction(&h->f_rk45_chain, h->module, "rmt_n2_rk45_chain") != hipSuccess)
-        h->f_rk45_chain = nullptr;
-    if (hipModuleGetFunction(&h->f_multistep, h->module, "rmt_n2_multistep_mem") != hipSuccess)
-        h->f_multistep = nullptr;
-    if (hipModuleGetFunction(&h->f_rk4_chain, h->module, "rmt_n2_rk4_chain") != hipSuccess)
-        h->f_rk4_chain = nullptr;
-    if (hipModuleGetFunction(&h->f_rk4_chain_redo, h->module, "rmt_n2_rk4_chain_redo") != hipSuccess)
-        h->f_rk4_chain_redo = nullptr;
-    if (hipModuleGetFunction(&h->f_ros4, h->module, "rmt_n2_ros4_mem") != hipSuccess)
-        h->f_ros4 = nullptr;
-    if (hipModuleGetFunction(&h->f_n1, h->module, "rmt_n1_ros4") != hipSuccess) h->f_n1 = nullptr;
-    if (hipModuleGetFunction(&h->f_ros4_chain, h->module, "rmt_n2_ros4_chain") != hipSuccess) h->f_ros4_chain = nullptr;
+    // The kernels of the code object; the optional ones depend on what it was generated with.  rmt_n2_rk4_reg_redo /
+    // rmt_n2_rk4_chain_redo: code objects whose RK4 stepper caches the temperature-only rate constants (RMT_KCACHE) carry
+    // the plain stepper as a second kernel - it re-integrates the reactors the cached one gave up on.
+    static const struct { const char* name; hipFunction_t rmt_n2_handle::*f; bool required; } kernels[] = {
+        {"rmt_n2_rhs", &rmt_n2_handle::f_rhs, true},
+        {"rmt_n2_rk4_reg", &rmt_n2_handle::f_rk4_reg, true},
+        {"rmt_n2_rk4_mem", &rmt_n2_handle::f_rk4_mem, true},
+        {"rmt_n2_rk4_reg_redo", &rmt_n2_handle::f_rk4_redo, false},
+        {"rmt_n2_rk45_reg", &rmt_n2_handle::f_rk45_reg, false},
+        {"rmt_n2_rk45_mem", &rmt_n2_handle::f_rk45_mem, false},
+        {"rmt_n2_rk45_chain", &rmt_n2_handle::f_rk45_chain, false},
+        {"rmt_n2_multistep_mem", &rmt_n2_handle::f_multistep, false},
+        {"rmt_n2_rk4_chain", &rmt_n2_handle::f_rk4_chain, false},
+        {"rmt_n2_rk4_chain_redo", &rmt_n2_handle::f_rk4_chain_redo, false},
+        {"rmt_n2_ros4_mem", &rmt_n2_handle::f_ros4, false},
+        {"rmt_n1_ros4", &rmt_n2_handle::f_n1, false},
+        {"rmt_n2_ros4_chain", &rmt_n2_handle::f_ros4_chain, false},
+    };
+    for (const auto& k : kernels) {
+        const hipError_t e = hipModuleGetFunction(&(h->*k.f), h->module, k.name);
+        if (e == hipSuccess) continue;
+        h->*k.f = nullptr;
+        if (!k.required) continue;
+        fail("hipModuleGetFunction(\"%s\") failed: %s", k.name, hipGetErrorString(e));
+        rmt_n2_destroy(h);
+        return 1;
+    }
     (void)hipGetLastError();
     CREATE_OK(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
+    const size_t mbytes = member_bytes(h);
     CREATE_OK(hipMalloc((void**)&h->d_members, mbytes));
     CREATE_OK(hipMemcpy(h->d_members, p->members, mbytes, hipMemcpyHostToDevice));
     // one status word per reactor + one word behind them: how many reactor-launches the cached RK4 steppers handed to
@@ -305,7 +314,7 @@ extern "C" int rmt_n2_set_mode(rmt_n2_handle* h, int mode) {
 extern "C" int rmt_n2_set_members(rmt_n2_handle* h, const double* members) {
     if (!h || !members) return fail("null argument");
     ON_DEVICE(h);
-    const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
+    const size_t mbytes = member_bytes(h);
     HIP_OK(hipMemcpyAsync(h->d_members, members, mbytes, hipMemcpyHostToDevice, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
@@ -314,7 +323,7 @@ extern "C" int rmt_n2_set_members(rmt_n2_handle* h, const double* members) {
 extern "C" int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members) {
     if (!h || !members) return fail("null argument");
     ON_DEVICE(h);
-    const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
+    const size_t mbytes = member_bytes(h);
     HIP_OK(hipMemcpyAsync(h->d_members, members, mbytes, hipMemcpyHostToDevice, h->stream));
     return 0;
 }
@@ -322,14 +331,14 @@ extern "C" int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members)
 extern "C" int rmt_n2_get_members(rmt_n2_handle* h, double* members) {
     if (!h || !members) return fail("null argument");
     ON_DEVICE(h);
-    const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
+    const size_t mbytes = member_bytes(h);
     HIP_OK(hipMemcpyAsync(members, h->d_members, mbytes, hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
 static int ensure_work(rmt_n2_handle* h, size_t arrays, size_t extra_bytes = 0) {
-    const size_t need = arrays * (size_t)h->E * h->V * h->N * h->real_size + extra_bytes;
+    const size_t need = arrays * state_bytes(h) + extra_bytes;
     if (h->work_bytes >= need) return 0;
     if (h->d_work) {
         HIP_OK(hipStreamSynchronize(h->stream));
@@ -490,7 +499,7 @@ extern "C" int rmt_n2_rk4(rmt_n2_handle* h, void* y, double t0, double dt, int64
         void* backup = nullptr;
         unsigned *redo = nullptr, *falt = nullptr;
         if (h->f_rk4_chain_redo) {
-            const size_t state = (size_t)h->E * h->V * h->N * (h->fp32 ? 4 : 8);
+            const size_t state = state_bytes(h);
             if (!h->d_backup) {
                 HIP_OK(hipMalloc(&h->d_backup, state));
                 HIP_OK(hipMalloc((void**)&h->d_redo, 2 * (size_t)h->E * sizeof(unsigned)));
@@ -505,7 +514,7 @@ extern "C" int rmt_n2_rk4(rmt_n2_handle* h, void* y, double t0, double dt, int64
         // the input copied to the backup buffer the plain stepper reads
         const bool plain = h->f_rk4_chain_redo && !capturing(h) && plain_this_call(h);
         if (plain) {
-            const size_t state = (size_t)h->E * h->V * h->N * (h->fp32 ? 4 : 8);
+            const size_t state = state_bytes(h);
             HIP_OK(hipMemcpyAsync(h->d_backup, y, state, hipMemcpyDeviceToDevice, h->stream));
             HIP_OK(hipMemsetAsync(h->d_redo, 2, (size_t)h->E * sizeof(unsigned), h->stream));
         }
@@ -678,7 +687,7 @@ extern "C" int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* ou
     if (nout < 2 || !(rtol > 0) || !(atol >= 0) || !(h0 > 0)) return fail("bad N1 arguments");
     if (!h->f_n1) return fail("code object has no N1 kernel");
     ON_DEVICE(h);
-    const size_t mbytes = (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double);
+    const size_t mbytes = member_bytes(h);
     if (!h->d_members1) HIP_OK(hipMalloc((void**)&h->d_members1, mbytes));
     HIP_OK(hipMemcpyAsync(h->d_members1, members1, mbytes, hipMemcpyHostToDevice, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
@@ -729,9 +738,34 @@ extern "C" int rmt_n2_status(rmt_n2_handle* h, uint32_t* flags_host) {
 #define RMT_N2_MONITOR_WAVE_BYTES 8192
 #define RMT_N2_MONITOR_ROWS_PER_CU 4
 
-struct rmt_n2_monitor {
-    int device = 0, n_cus = 0, last_rows_per_block = 0;
-    hipModule_t module = nullptr;
+// What the monitor and the controller share: a module loaded on the device that was current at creation
+struct SideModule { int device = 0; hipModule_t module = nullptr; };
+struct SideKernel { const char* name; hipFunction_t* f; };
+
+static void side_unload(SideModule* m) {
+    DeviceGuard guard_(m->device);
+    if (m->module) (void)hipModuleUnload(m->module);
+}
+
+// the loader of both (``who``: the entry point, ``what``: "monitor" / "controller", for the error texts); a module that
+// lacks one of its kernels is unloaded again
+static int side_load(SideModule* m, const char* who, const char* what, const void* code,
+                     std::initializer_list<SideKernel> kernels) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail("no HIP device available: the %s has no CPU fallback", what);
+    hipError_t e = hipGetDevice(&m->device);
+    if (e == hipSuccess) e = hipModuleLoadData(&m->module, code);
+    for (const SideKernel& k : kernels)
+        if (e == hipSuccess) e = hipModuleGetFunction(k.f, m->module, k.name);
+    if (e == hipSuccess) return 0;
+    fail("%s: %s", who, hipGetErrorString(e));
+    side_unload(m);
+    return 1;
+}
+
+struct rmt_n2_monitor : SideModule {
+    int n_cus = 0, last_rows_per_block = 0;
     hipFunction_t f64 = nullptr, f32 = nullptr;
 };
 
@@ -739,23 +773,20 @@ extern "C" const char* rmt_n2_monitor_source(void) { return k_monitor_source; }
 
 extern "C" void rmt_n2_monitor_destroy(rmt_n2_monitor* m) {
     if (!m) return;
-    DeviceGuard guard_(m->device);
-    if (m->module) (void)hipModuleUnload(m->module);
+    side_unload(m);
     delete m;
 }
 
 extern "C" int rmt_n2_monitor_create(const void* code, size_t size, rmt_n2_monitor** out) {
     if (!code || !size || !out) return fail("rmt_n2_monitor_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail("no HIP device available: the monitor has no CPU fallback");
     rmt_n2_monitor* m = new rmt_n2_monitor();
-    hipError_t e = hipGetDevice(&m->device);
-    if (e == hipSuccess) e = hipModuleLoadData(&m->module, code);
-    if (e == hipSuccess) e = hipModuleGetFunction(&m->f64, m->module, "rmt_n2_monitor_rows_f64");
-    if (e == hipSuccess) e = hipModuleGetFunction(&m->f32, m->module, "rmt_n2_monitor_rows_f32");
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&m->n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
+    if (side_load(m, "rmt_n2_monitor_create", "monitor", code,
+                  {{"rmt_n2_monitor_rows_f64", &m->f64}, {"rmt_n2_monitor_rows_f32", &m->f32}})) {
+        delete m;
+        return 1;
+    }
+    const hipError_t e = hipDeviceGetAttribute(&m->n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
     if (e != hipSuccess) {
         fail("rmt_n2_monitor_create: %s", hipGetErrorString(e));
         rmt_n2_monitor_destroy(m);
@@ -810,9 +841,7 @@ extern "C" int rmt_n2_monitor_last_rows_per_block(const rmt_n2_monitor* m) { ret
 #define RMT_N2_CONTROL_BLOCK 256
 #define RMT_N2_CONTROL_MAX_GRID 32
 
-struct rmt_n2_control {
-    int device = 0;
-    hipModule_t module = nullptr;
+struct rmt_n2_control : SideModule {
     hipFunction_t f_update = nullptr;
 };
 
@@ -820,24 +849,16 @@ extern "C" const char* rmt_n2_control_source(void) { return k_control_source; }
 
 extern "C" void rmt_n2_control_destroy(rmt_n2_control* c) {
     if (!c) return;
-    DeviceGuard guard_(c->device);
-    if (c->module) (void)hipModuleUnload(c->module);
+    side_unload(c);
     delete c;
 }
 
 extern "C" int rmt_n2_control_create(const void* code, size_t size, rmt_n2_control** out) {
     if (!code || !size || !out) return fail("rmt_n2_control_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail("no HIP device available: the controller has no CPU fallback");
     rmt_n2_control* c = new rmt_n2_control();
-    hipError_t e = hipGetDevice(&c->device);
-    if (e == hipSuccess) e = hipModuleLoadData(&c->module, code);
-    if (e == hipSuccess) e = hipModuleGetFunction(&c->f_update, c->module, "rmt_n2_control_update_f64");
-    if (e != hipSuccess) {
-        fail("rmt_n2_control_create: %s", hipGetErrorString(e));
-        rmt_n2_control_destroy(c);
+    if (side_load(c, "rmt_n2_control_create", "controller", code, {{"rmt_n2_control_update_f64", &c->f_update}})) {
+        delete c;
         return 1;
     }
     *out = c;

@@ -104,49 +104,61 @@ def kernel_template():
     return lib().rmt_n2_kernel_template().decode()
 
 
-def monitor_source():
-    """The monitor's translation unit (csrc/monitor_kernels.inc, embedded in the library next to the template)."""
-    return lib().rmt_n2_monitor_source().decode()
-
-
-def monitor_code(arch="gfx950"):
-    """Code object of the monitor kernels from the in-tree cache (compiled on first use; works without a GPU)."""
+def _side_code(prefix, src, arch, opts=""):
+    """Code object of one of the two mechanism-independent side modules from the in-tree cache (compiled on first use;
+    works without a GPU)."""
     import hashlib
-    src = monitor_source()
-    return compile_cached(src, "monitor-" + hashlib.sha256(src.encode()).hexdigest()[:24], arch)
+    return compile_cached(src, "%s-%s" % (prefix, hashlib.sha256(src.encode()).hexdigest()[:24]), arch, opts)
 
 
-class Monitor:
-    """rmt_n2_monitor on the current device: row reductions of a state tensor [E][V][N] into out [E][V][5] doubles
-    = {y[N-1], max, argmax, min, max|dydt|} (include/rmt_n2.h).  Independent of any mechanism."""
+class _SideModule:
+    """What Monitor and Control share: the code buffer, the handle ``h`` of rmt_n2_<kind>_create on the current device,
+    and its release."""
+    kind = code_for = None           # "monitor" / "control", the infix of the C exports; monitor_code / control_code
 
     def __init__(self, arch="gfx950", code=None):
-        code = monitor_code(arch) if code is None else code
+        code = self.code_for(arch) if code is None else code
         self._code = C.create_string_buffer(code, len(code))
-        m = C.c_void_p()
-        check(lib().rmt_n2_monitor_create(C.cast(self._code, C.c_void_p), len(code), C.byref(m)))
-        self.m = m
-
-    def reduce(self, stream, y_ptr, dydt_ptr, E, V, N, fp32, out_ptr):
-        """Enqueue the reduction on `stream` (a hipStream_t as integer); nothing is synchronised."""
-        check(lib().rmt_n2_monitor_reduce(self.m, C.c_void_p(stream), C.c_void_p(y_ptr),
-                                          C.c_void_p(dydt_ptr) if dydt_ptr else None, int(E), int(V), int(N),
-                                          int(bool(fp32)), C.c_void_p(out_ptr)))
-
-    def last_rows_per_block(self):
-        """4: the last reduce ran one wave per row, 1: one workgroup per row."""
-        return int(lib().rmt_n2_monitor_last_rows_per_block(self.m))
+        h = C.c_void_p()
+        check(getattr(lib(), "rmt_n2_%s_create" % self.kind)(C.cast(self._code, C.c_void_p), len(code), C.byref(h)))
+        self.h = h
 
     def close(self):
-        if getattr(self, "m", None):
-            lib().rmt_n2_monitor_destroy(self.m)
-            self.m = None
+        if getattr(self, "h", None):
+            getattr(lib(), "rmt_n2_%s_destroy" % self.kind)(self.h)
+            self.h = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+def monitor_source():
+    """The monitor's translation unit (csrc/monitor_kernels.inc, embedded in the library next to the template)."""
+    return lib().rmt_n2_monitor_source().decode()
+
+
+def monitor_code(arch="gfx950"):
+    """Code object of the monitor kernels (_side_code)."""
+    return _side_code("monitor", monitor_source(), arch)
+
+
+class Monitor(_SideModule):
+    """rmt_n2_monitor on the current device: row reductions of a state tensor [E][V][N] into out [E][V][5] doubles
+    = {y[N-1], max, argmax, min, max|dydt|} (include/rmt_n2.h).  Independent of any mechanism."""
+    kind, code_for = "monitor", staticmethod(monitor_code)
+
+    def reduce(self, stream, y_ptr, dydt_ptr, E, V, N, fp32, out_ptr):
+        """Enqueue the reduction on `stream` (a hipStream_t as integer); nothing is synchronised."""
+        check(lib().rmt_n2_monitor_reduce(self.h, C.c_void_p(stream), C.c_void_p(y_ptr),
+                                          C.c_void_p(dydt_ptr) if dydt_ptr else None, int(E), int(V), int(N),
+                                          int(bool(fp32)), C.c_void_p(out_ptr)))
+
+    def last_rows_per_block(self):
+        """4: the last reduce ran one wave per row, 1: one workgroup per row."""
+        return int(lib().rmt_n2_monitor_last_rows_per_block(self.h))
 
 
 CONTROL_OPTS = "-ffp-contract=off"       # the control law: one rounded fp64 operation each, reproducible in numpy
@@ -158,41 +170,21 @@ def control_source():
 
 
 def control_code(arch="gfx950"):
-    """Code object of the control kernel from the in-tree cache (compiled on first use, with floating-point contraction
-    off; works without a GPU)."""
-    import hashlib
-    src = control_source()
-    return compile_cached(src, "control-" + hashlib.sha256(src.encode()).hexdigest()[:24], arch, CONTROL_OPTS)
+    """Code object of the control kernel, compiled with floating-point contraction off (_side_code)."""
+    return _side_code("control", control_source(), arch, CONTROL_OPTS)
 
 
-class Control:
+class Control(_SideModule):
     """rmt_n2_control on the current device: the sampled PI controller's kernel (include/rmt_n2.h).  Independent of any
     mechanism; ``update`` enqueues one kernel on the stream of the N2 handle whose device rows it writes."""
-
-    def __init__(self, arch="gfx950", code=None):
-        code = control_code(arch) if code is None else code
-        self._code = C.create_string_buffer(code, len(code))
-        c = C.c_void_p()
-        check(lib().rmt_n2_control_create(C.cast(self._code, C.c_void_p), len(code), C.byref(c)))
-        self.c = c
+    kind, code_for = "control", staticmethod(control_code)
 
     def update(self, handle, y_ptr, V, N, params_ptr, setpoint_ptr, state_ptr, log_ptr, tail_at, field, hold=False):
         """Enqueue an update (or, with ``hold``, the rewrite of the held value); nothing is synchronised."""
         def ptr(p):
             return C.c_void_p(p) if p else None
-        check(lib().rmt_n2_control_update(self.c, handle, ptr(y_ptr), int(V), int(N), ptr(params_ptr), ptr(setpoint_ptr),
+        check(lib().rmt_n2_control_update(self.h, handle, ptr(y_ptr), int(V), int(N), ptr(params_ptr), ptr(setpoint_ptr),
                                           ptr(state_ptr), ptr(log_ptr), int(tail_at), int(field), int(bool(hold))))
-
-    def close(self):
-        if getattr(self, "c", None):
-            lib().rmt_n2_control_destroy(self.c)
-            self.c = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def compile_source(source, arch="gfx950", extra_opts=""):

@@ -9,14 +9,14 @@
   is a sample and there are K = 1 + tNo*m of them.  "times": the samples are exactly {0} and the given times.
 * A sample time within schedule.MERGE_TOL * period of an output time or of a schedule breakpoint IS that time.
 * The integration is split at the sample times the way "schedule" splits it at its breakpoints: the launch list is the
-  sorted union of output times, breakpoints and sample times.  Only launches that end at an output time are packed,
-  only launches that end at a sample time are monitored.  A monitored run therefore takes exactly the launches of an
+  sorted union of output times, breakpoints and sample times (launches.merge).  Only launches that end at an output
+  time are packed, only launches that end at a sample time are monitored.  A monitored run takes exactly the launches of an
   unmonitored run whose output times are that union - and computes the same states bit for bit.
 * At a sample the state stays where it is: a reduction kernel (csrc/monitor_kernels.inc) writes, per member and
   variable, {outlet value, max, argmax, min, max|dy/dt|} into slice k of ONE device buffer [K][E][V][5], which is
   copied to the host once, at the end of the run.
 
-Host side only (numpy): parsing and validation, the sample times, the refined launch list and the conversion of the
+Host side only (numpy): parsing and validation, the sample times and the conversion of the
 raw numbers to the result entry resModel["monitor"].
 """
 import numpy as np
@@ -69,25 +69,6 @@ class Monitor:
             raise ValueError("solver-config 'monitor': %r asks for %d samples of %d members x %d variables = %d bytes "
                              "of monitor buffer, more than the %d allowed - lower 'samples'"
                              % ("samples" if self.given == "samples" else "times", self.K, E, V, need, cap))
-
-    def refine(self, launches, period):
-        """Launch list [(t0, t1, k_out, k_sample)] from a list [(t0, t1, k_out)] that covers [0, period] (the plain
-        output intervals, or Schedule.boundaries): split at every sample time that is not yet a mark; k_sample = index
-        of the sample the launch ends at, None when it ends at an output time or breakpoint only.  A sample within
-        MERGE_TOL * period of a mark is that mark."""
-        tol = MERGE_TOL*float(period)
-        marks = [[float(launches[0][0]), None, None]] + [[float(t1), k, None] for _, t1, k in launches]
-        at = np.array([m[0] for m in marks])
-        extra = []
-        for ks, t in enumerate(self.times):
-            j = int(np.argmin(np.abs(at - t)))
-            if abs(at[j] - t) <= tol:
-                marks[j][2] = ks
-                self.times[ks] = at[j]
-            else:
-                extra.append([float(t), None, ks])
-        marks = sorted(marks + extra, key=lambda m: m[0])
-        return [(marks[i][0], marks[i + 1][0], marks[i + 1][1], marks[i + 1][2]) for i in range(len(marks) - 1)]
 
 
 def parse(modelInput, tNo, has_schedule=None):

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from . import control, hipbind, monitor, plan, schedule
+from . import control, hipbind, launches, monitor, plan, schedule
 from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
@@ -413,8 +413,7 @@ class N2Device:
         self.block, self.npt, self.defines, self.features = cp.block, cp.npt, cp.defines, cp.features
         self.lds_state = mech.lds_state(self.fp32, self.block, self.npt, cp.lds_state)
         if code is None:      # an ensemble rank may receive rank 0's code object instead
-            code = compile_plan(mech, self.fp32, cp, torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0],
-                                extra_opts)
+            code = compile_plan(mech, self.fp32, cp, device_arch(self.device), extra_opts)
         self._code = C.create_string_buffer(code, len(code))
         p = hipbind.Plan()
         p.abi_version = hipbind.ABI_VERSION
@@ -503,9 +502,8 @@ class N2Device:
         assert out.is_cuda and out.dtype == self.torch.float64 and out.is_contiguous()
         assert out.numel() == self.E*self.mech.V*monitor.SLOTS, "monitor output must be [E][V][5] doubles"
         if getattr(self, "_mon", None) is None:
-            arch = self.torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]
             with self.torch.cuda.device(self.device):
-                self._mon = hipbind.Monitor(arch)
+                self._mon = hipbind.Monitor(device_arch(self.device))
         dydt = self.rhs(y) if residual else None       # (stays allocated until the stream is past the reduce: torch's
         #                                                 caching allocator hands memory out in stream order)
         self._mon.reduce(self._stream, y.data_ptr(), dydt.data_ptr() if residual else 0, self.E, self.mech.V, self.N,
@@ -836,12 +834,16 @@ def resolve_ivp(ivp):
     return ivp
 
 
-def device_arch():
-    """Architecture the JIT targets: the visible GPU's, gfx950 when there is none (cross-compile)."""
+def device_arch(device=None):
+    """Architecture the JIT targets: that of ``device``; without one the current GPU's, gfx950 when none is visible
+    (cross-compile)."""
+    if device is not None:
+        import torch
+        return torch.cuda.get_device_properties(device).gcnArchName.split(":")[0]
     try:
         import torch
         if torch.cuda.is_available():
-            return torch.cuda.get_device_properties(torch.cuda.current_device()).gcnArchName.split(":")[0]
+            return device_arch(torch.cuda.current_device())
     except Exception:
         pass
     return "gfx950"
@@ -976,12 +978,12 @@ def outlet_only(cfg):
 
 
 class Forcing:
-    """A parsed schedule bound to one run: the launch list (output times and breakpoints), the local members' ordinary
-    rows, and the refresh of the device rows ahead of every launch (schedule.Schedule.forced_rows)."""
+    """A parsed schedule bound to one run: the local members' ordinary rows and the refresh of the device rows ahead of
+    every launch of the run's list (schedule.Schedule.forced_rows)."""
 
-    def __init__(self, sched, period, tNo, N, want_mode=None):
+    def __init__(self, sched, walk, N, want_mode=None):
         self.sched, self.N, self.want_mode = sched, int(N), want_mode
-        self.launches = sched.boundaries(period, tNo)
+        self.first = walk[0].t0, walk[0].t1
         self.rows = self.named = None
         self.modes = {}
 
@@ -992,8 +994,7 @@ class Forcing:
                 raise ValueError("solver-config 'schedule': %d member rows for a schedule of %d members"
                                  % (len(named), self.sched.E))
             self.rows, self.named = np.array(rows, dtype=np.float64), list(named)
-        t0, t1, _ = self.launches[0]
-        return self.sched.forced_rows(self.rows, self.named, t0, t1)
+        return self.sched.forced_rows(self.rows, self.named, *self.first)
 
     def fix_mode(self, dev, ivp):
         mode = forced_mode(ivp, self.N, dev.block, dev.npt, self.want_mode)
@@ -1018,9 +1019,8 @@ class ControlLoop:
         d = getattr(dev, "d45", dev)                  # ("hip-auto": both devices live on the same GPU)
         torch = d.torch
         self.ctl, self.E, self.field = ctl, ctl.E, ctl.field
-        arch = torch.cuda.get_device_properties(d.device).gcnArchName.split(":")[0]
         with torch.cuda.device(d.device):
-            self.kernel = hipbind.Control(arch)
+            self.kernel = hipbind.Control(device_arch(d.device))
         self.params = torch.from_numpy(ctl.params()).to(d.device)
         self.setpoints = torch.from_numpy(np.ascontiguousarray(ctl.setpoints)).to(d.device)
         self.state = torch.zeros((ctl.E, control.STATE), dtype=torch.float64, device=d.device)
@@ -1031,41 +1031,28 @@ class ControlLoop:
         self.kernel.close()
 
 
-def launch_list(opTSpan, forcing=None, mon=None, ctl=None):
-    """The launches of a run [(t0, t1, index of the output time the launch ends at or None, index of the monitor sample it
-    ends at or None, index of the control sample taken at its start or None)]: the sorted union of output times, schedule
-    breakpoints, monitor samples and control samples."""
-    tNo = len(opTSpan) - 1
-    launches = forcing.launches if forcing is not None else \
-        [(float(opTSpan[i]), float(opTSpan[i + 1]), i + 1) for i in range(tNo)]
-    launches = mon.refine(launches, float(opTSpan[-1])) if mon is not None else [l + (None,) for l in launches]
-    return ctl.refine(launches, float(opTSpan[-1])) if ctl is not None else [l + (None,) for l in launches]
-
-
 PIPELINE_BYTES = 1 << 30       # pinned host memory one batch of queued output intervals may hold (integrate_intervals)
 
 
-def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_interval, sync=None, outlet=False,
+def integrate_intervals(dev, y, cfg, ivp, walk, n_members, zNo, quiet, on_interval, sync=None, outlet=False,
                         forcing=None, mon=None, ctl=None):
-    """The reference's time loop (pbHomoReactor.py:3589-3690, pbReactor.py:711-762): one device
-    launch per output interval; ``on_interval(i, t1, Y_host)`` packs the end state ([E][V*zNo], or [E][V] = the
-    outlet node with ``outlet``).  With ``sync`` (multi-rank ensemble) a failure on any rank is raised on every
-    rank before the next gather.
-    ``forcing`` (solver-config "schedule"): the walk goes over output times AND breakpoints (Forcing.launches; only a
-    launch that ends at an output time is packed), and the device rows are refreshed before each launch is queued.
-    ``mon`` (a monitor.Monitor, solver-config "monitor"): the walk is split at the sample times as well; behind a launch
-    that ends at sample k the row reductions of the state are queued into slice k of ONE device buffer [K][E][V][5]
-    (sample 0 before the first launch; with "residual" behind rmt_n2_rhs at that state).  Nothing is copied or
-    synchronised per sample: the buffer comes back once, at the end, as ``stats["monitor-raw"]`` ([K][E_local][V][5];
-    the callers pop it).  A run that raises on flags returns no monitor.
-    ``ctl`` (a control.Control, solver-config "control"; needs ``forcing``): the walk is split at the control samples too.
-    The order in the stream for every launch is: refresh of the rows, the controller's kernel, the stepper - the update
-    when the launch starts at a sample time, else (once a sample has been taken) the rewrite of the held value, because
-    the refresh uploads whole rows.  The log [K][E_local][4] comes back once, as ``stats["control-raw"]``."""
+    """The reference's time loop (pbHomoReactor.py:3589-3690, pbReactor.py:711-762): one device launch per entry of
+    ``walk`` (the list of launches.merge: without "schedule", "monitor" and "control" one per output interval);
+    ``on_interval(i, t1, Y_host)`` packs the end state ([E][V*zNo], or [E][V] = the outlet node with ``outlet``) of a launch
+    that ends at an output time.  With ``sync`` (multi-rank ensemble) a failure on any rank is raised on every rank before
+    the next gather.  Returns (stats, raw): the statistics record and the one-off device buffers
+    {"monitor": [K][E_local][V][5] or None, "control": [K][E_local][4] or None}.
+    ``forcing`` (solver-config "schedule"): the device rows are refreshed before each launch is queued.
+    ``mon`` (a monitor.Monitor, solver-config "monitor"): behind a launch that ends at sample k the row reductions of the
+    state are queued into slice k of ONE device buffer [K][E][V][5] (sample 0 before the first launch; with "residual"
+    behind rmt_n2_rhs at that state).  Nothing is copied or synchronised per sample: the buffer comes back once, at the
+    end.  A run that raises on flags returns no monitor.
+    ``ctl`` (a control.Control, solver-config "control"; needs ``forcing``): the order in the stream for every launch is:
+    refresh of the rows, the controller's kernel, the stepper - the update when the launch starts at a sample time, else
+    (once a sample has been taken) the rewrite of the held value, because the refresh uploads whole rows.  The log comes
+    back once, at the end."""
     import torch
-    tNo = len(opTSpan) - 1
-    launches = launch_list(opTSpan, forcing, mon, ctl)
-    nL = len(launches)
+    nL = len(walk)
     loop = ControlLoop(ctl, dev) if ctl is not None else None
     mbuf = None
     if mon is not None:
@@ -1124,49 +1111,50 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
     def queue(lo, hi):
         staged = []
         for i in range(lo, hi):
-            t0, t1, kout, ksample, kctl = launches[i]
+            launch = walk[i]
             _progress(i + 1, nL + 1, quiet)
             # (the page-locked rows of a queued refresh stay alive until the batch has landed)
-            rows = forcing.refresh(dev, t0, t1, queued) if forcing is not None else None
-            if loop is not None and (kctl is not None or loop.taken):
-                dev.control(y, loop, kctl)                       # behind the refresh, ahead of the stepper
-                loop.taken += kctl is not None
-            step(i, t0, t1)
-            sample(ksample)                                      # queued right behind its launch, into slice ksample
+            rows = forcing.refresh(dev, launch.t0, launch.t1, queued) if forcing is not None else None
+            if loop is not None and (launch.control is not None or loop.taken):
+                dev.control(y, loop, launch.control)             # behind the refresh, ahead of the stepper
+                loop.taken += launch.control is not None
+            step(i, launch.t0, launch.t1)
+            sample(launch.sample)                                # queued right behind its launch, into its slice
             state = counters = landed = None
-            if kout is not None:
+            if launch.out is not None:
                 state = to_host(y.reshape(E_loc, -1, zNo)[:, :, zNo - 1] if outlet else y)
             if adaptive:
                 counters = to_host(dev._stats)
             if queued:
                 landed = torch.cuda.Event()
                 landed.record()
-            staged.append((kout, state, counters, landed, rows))
+            staged.append((launch, state, counters, landed, rows))
         if sync is not None:
             dev.raise_on_flags()
         return staged
 
-    _progress(0, tNo + 1, quiet)
+    _progress(0, nL + 1, quiet)
     guarded(sync, sample, 0)
+    raw = {"monitor": None, "control": None}
     try:
         for lo in range(0, nL, batch):
-            for kout, state, counters, landed, _ in guarded(sync, queue, lo, min(nL, lo + batch)):
+            for launch, state, counters, landed, _ in guarded(sync, queue, lo, min(nL, lo + batch)):
                 if landed is not None:                                # packing launch i while the device is at i+1, i+2, ...
                     landed.synchronize()
                 if counters is not None:
                     acc, rej = step_counts(counters.numpy())
                     stats["accepted"] = acc if stats["accepted"] is None else stats["accepted"] + acc
                     stats["rejected"] = rej if stats["rejected"] is None else stats["rejected"] + rej
-                if kout is not None:                                  # (None: a breakpoint or a sample time - nothing to pack)
-                    on_interval(kout - 1, float(opTSpan[kout]), state.numpy().astype(np.float64))
+                if launch.out is not None:                            # (None: a breakpoint or a sample time - nothing to pack)
+                    on_interval(launch.out - 1, launch.t1, state.numpy().astype(np.float64))
             if sync is None:
                 dev.raise_on_flags()                                  # (sticky status words: whatever a launch of the batch flagged)
         if ivp == "hip-auto":
             stats["method-per-interval"] = list(dev.choices)
         if mbuf is not None:
-            stats["monitor-raw"] = mbuf.cpu().numpy()                 # the ONE copy of the monitor buffer
+            raw["monitor"] = mbuf.cpu().numpy()                       # the ONE copy of the monitor buffer
         if loop is not None:
-            stats["control-raw"] = loop.log.cpu().numpy()            # the ONE copy of the controllers' log
+            raw["control"] = loop.log.cpu().numpy()                   # the ONE copy of the controllers' log
     finally:
         if loop is not None:
             loop.close()
@@ -1176,15 +1164,14 @@ def integrate_intervals(dev, y, cfg, ivp, opTSpan, n_members, zNo, quiet, on_int
         stats = finish_stats(stats, ivp, n_members, nL, zNo, dev.jacobian_evals)
     if ivp == "hip-auto":
         stats["rhs_evals"] = dev.rhs_evals          # includes the probe and any abandoned explicit attempt
-    return stats
+    return stats, raw
 
 
-def attach_monitor(stats, mon, sync, convert):
+def attach_monitor(raw, sync, convert):
     """The monitor entries of every member, on the process that returns the results: the raw buffer integrate_intervals
-    left in ``stats`` ([K][E_local][V][5]; removed from the record), gathered to rank 0 ONCE in a multi-rank job, each
-    member converted by ``convert(e, raw [K][V][5])``.  None without a monitor and on the other ranks."""
-    raw = stats.pop("monitor-raw", None)
-    if mon is None or raw is None:
+    returned ([K][E_local][V][5]), gathered to rank 0 ONCE in a multi-rank job, each member converted by
+    ``convert(e, raw [K][V][5])``.  None without a monitor and on the other ranks."""
+    if raw is None:
         return None
     raw = np.ascontiguousarray(np.swapaxes(raw, 0, 1))            # [E_local][K][V][5]
     if sync is not None:
@@ -1270,13 +1257,21 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
     mon = monitor.parse(modelInput, tNo)
     if mon is not None:
         mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
+    # the ONE launch list of the run; a sample that fell on a mark carries that mark's time from here on (result entries)
+    walk, sample_times, control_times = launches.merge(
+        opT, tNo, forced_by.times if forced_by is not None else (), mon.times if mon is not None else None,
+        ctl.times if ctl is not None else None)
+    if mon is not None:
+        mon.times = sample_times
+    if ctl is not None:
+        ctl.times = control_times
     forcing = None
     if forced_by is not None:
         if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
             raise NotImplementedError("solver-config 'schedule' with the stiff stepper needs a mechanism of at most 8 "
                                       "variables per node (this one has %d): its four-lane form does not carry the "
                                       "forcing - use ivp 'hip-rk45' or 'hip-rk4'" % mech.V)
-        forcing = Forcing(forced_by if sync is None else forced_by.members(sync.lo, sync.hi), opT, tNo, zNo,
+        forcing = Forcing(forced_by if sync is None else forced_by.members(sync.lo, sync.hi), walk, zNo,
                           cfg.get('device-mode'))
         if ivp == "hip-rk4" and block is None:
             # the geometry of ONE workgroup per reactor (no chunks: the chained kernels do not carry the forcing)
@@ -1308,16 +1303,16 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
             if Yg is not None:
                 for e, pk in enumerate(pack_all(Yg, named, mech, 1 if outlet else zNo, t1)):
                     packs[e].append(pk)
-        stats = integrate_intervals(dev, y, cfg, ivp, opTSpan, len(named_local), zNo, quiet or not packer, on_interval,
-                                    sync, outlet, forcing, mon, ctl)
-        logs = stats.pop("control-raw", None)                          # [K][E][4]
-        monitors = attach_monitor(stats, mon, sync, lambda e, raw: monitor.result_entry(
-            raw, mon.times, mech, zNo, named[e], model, inputs[e]['reactor']['ReLe'], mon.residual))
+        stats, raw = integrate_intervals(dev, y, cfg, ivp, walk, len(named_local), zNo, quiet or not packer,
+                                         on_interval, sync, outlet, forcing, mon, ctl)
+        logs = raw["control"]                                          # [K][E][4]
+        monitors = attach_monitor(raw["monitor"], sync, lambda e, r: monitor.result_entry(
+            r, mon.times, mech, zNo, named[e], model, inputs[e]['reactor']['ReLe'], mon.residual))
         if forcing is not None:
             # which kernel forms ran: "reg" = the on-chip steppers, "mem" = the memory-resident ones; and what
             # rmt_n2_last_geometry reports for the last launch (workgroups per reactor, teams)
             stats["device-mode"] = dict(forcing.modes)
-            stats.setdefault("launches", len(forcing.launches))       # (a monitored run: its refined list's)
+            stats.setdefault("launches", len(walk))            # (a monitored or controlled run has it already)
             stats["last-geometry"] = dev.last_geometry()
     finally:
         dev.close()

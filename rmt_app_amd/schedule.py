@@ -32,12 +32,13 @@
 * Ensembles: the breakpoint times come from the base input; a member may carry its own values under its
   own solver-config.schedule; with "relative": True one schedule applies to every member of a T/P sweep.
 
-Host side only (numpy): parsing and validation, the launch boundaries, per launch and member the values at
+Host side only (numpy): parsing and validation, per launch and member the values at
 the launch start and the slopes, and ``rows_at(t)`` - ordinary member rows with the forced fields at time t.
 """
 import numpy as np
 
 from . import plan
+from .launches import MERGE_TOL     # noqa: F401  (a breakpoint this close, relative to the period, to an output time IS it)
 
 # schedule key -> (where the member's own constant lives in the model input, unit)
 QUANTITIES = {
@@ -50,7 +51,6 @@ COMPOSITION = "inlet-concentration"       # [K][S] per member, beside the three 
 KEYS = ("time", "relative") + ORDER + (COMPOSITION,)
 TAIL = 4          # doubles a forced member row carries behind the ordinary ones: t_ref and the three slopes
 #                   (a schedule that moves the composition: S more, the slopes of CIN - Schedule.tail)
-MERGE_TOL = 1e-12     # a breakpoint this close (relative to the period) to an output time IS that output time
 
 
 def _own(mi, key):
@@ -87,20 +87,6 @@ class Schedule:
         """the RMT_FORCING value of the code object that evaluates this schedule (csrc/kernels/11_forcing.inc)"""
         return "1" if self.conc is None else "2"
 
-    # -- where the integration is split
-    def boundaries(self, period, tNo):
-        """Launch list [(t0, t1, k)] covering [0, period]: split at the output times linspace(0, period, tNo + 1) and at
-        every distinct breakpoint inside (0, period); k = index of the output time the launch ends at, None when it ends
-        at a breakpoint (breakpoints add no entries to the result)."""
-        out = np.linspace(0.0, float(period), int(tNo) + 1)
-        marks = [(float(t), k) for k, t in enumerate(out)]
-        tol = MERGE_TOL*float(period)
-        for b in np.unique(self.times):
-            if tol < b < period - tol and np.min(np.abs(out - b)) > tol:
-                marks.append((float(b), None))
-        marks.sort(key=lambda m: m[0])
-        return [(marks[i][0], marks[i + 1][0], marks[i + 1][1]) for i in range(len(marks) - 1)]
-
     # -- the piecewise-linear functions
     def _segment(self, t, side):
         T = self.times
@@ -128,7 +114,7 @@ class Schedule:
 
     def launch(self, t0, t1):
         """(values [E][3] at t0, slopes [E][3] per second) of the ONE linear piece that holds over the launch (t0, t1)
-        - the launch must not straddle a breakpoint (``boundaries`` sees to that)."""
+        - the launch must not straddle a breakpoint (launches.merge sees to that)."""
         return self._launch(self.values, t0, t1)
 
     def conc_launch(self, t0, t1):

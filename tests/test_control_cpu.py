@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import inputs as INP
-from rmt_app_amd import control, hipbind, isa, monitor, plan, rmtExe, schedule
+from rmt_app_amd import control, hipbind, isa, launches, monitor, plan, rmtExe, schedule
 from rmt_app_amd import n2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -133,7 +133,8 @@ def test_members_override_the_law_not_the_times(capsys):
     assert np.array_equal(sched.values[:, :, 0], [[523.0, 5.0e6, 523.0], [523.0, 5.0e6, 523.0], [523.0, 4.8e6, 523.0]])
     span = np.linspace(0.0, 0.4, 5)
     assert sched.forcing_level == "1"
-    assert sched.boundaries(0.4, 4) == [(float(span[i]), float(span[i + 1]), i + 1) for i in range(4)]
+    assert [l[:3] for l in launches.merge(0.4, 4, sched.times)[0]] == [(float(span[i]), float(span[i + 1]), i + 1)
+                                                                       for i in range(4)]
 
 
 # ----------------------------------------------------------------------------- sample times, launch lists
@@ -153,23 +154,22 @@ def test_refine_merges_with_output_times_breakpoints_and_monitor_samples():
     sched = schedule.parse(mi, None, "hip-rk4")
     ctl, forced_by = control.parse(mi, None, "hip-rk4", sched)
     assert forced_by is sched and ctl.K == 7
-    forcing = n2.Forcing(sched, 0.4, 2, 20)
     mon = monitor.parse(mi, 2)
-    L = n2.launch_list(np.linspace(0, 0.4, 3), forcing, mon, ctl)
+    L, _, times = launches.merge(0.4, 2, sched.times, mon.times, ctl.times)
     t = [l[0] for l in L] + [L[-1][1]]
     assert np.allclose(t, [0.0, 0.05, 0.1, 0.12, 0.15, 0.2, 0.25, 0.3, 0.35, 0.4], rtol=0, atol=1e-15)
     assert all(a[1] == b[0] for a, b in zip(L[:-1], L[1:]))
     # (t0, t1, output ended at, monitor sample ended at, control sample taken at the start)
-    assert [l[2] for l in L] == [None, None, None, None, 1, None, None, None, 2]
-    assert [l[3] for l in L] == [None, 1, 2, None, None, None, None, None, None]
-    assert [l[4] for l in L] == [None, 0, 1, None, 2, 3, 4, 5, 6]
+    assert [l.out for l in L] == [None, None, None, None, 1, None, None, None, 2]
+    assert [l.sample for l in L] == [None, 1, 2, None, None, None, None, None, None]
+    assert [l.control for l in L] == [None, 0, 1, None, 2, 3, 4, 5, 6]
     # a sample that coincides with a breakpoint (0.15), with an output time (0.2) and with a monitor sample (0.1) carries
     # that mark's value, bit for bit
-    assert ctl.times[2] == 0.15 and ctl.times[3] == 0.2 and ctl.times[1] == 0.1 and L[5][0] == 0.2
+    assert times[2] == 0.15 and times[3] == 0.2 and times[1] == 0.1 and L[5].t0 == 0.2
     # a controller that starts at 0 samples ahead of the first launch
     ctl0, _ = control.parse(_input(start=0.0, **{"sample-time": 0.1}), None, "hip-rk4")
-    L0 = n2.launch_list(np.linspace(0, 0.4, 5), None, None, ctl0)
-    assert [l[4] for l in L0] == [0, 1, 2, 3] and len(L0) == 4
+    L0 = launches.merge(0.4, 4, controls=ctl0.times)[0]
+    assert [l.control for l in L0] == [0, 1, 2, 3] and len(L0) == 4
 
 
 def test_without_the_key_nothing_changes():
@@ -180,13 +180,17 @@ def test_without_the_key_nothing_changes():
     mi["solver-config"]["monitor"] = {"samples": 2}
     sched = schedule.parse(mi, None, "hip-rk4")
     assert control.parse(mi, None, "hip-rk4", sched) == (None, sched)
-    forcing, mon = n2.Forcing(sched, 0.4, 4, 20), monitor.parse(mi, 4)
+    mon = monitor.parse(mi, 4)
     span = np.linspace(0, 0.4, 5)
-    want = monitor.parse(mi, 4).refine(sched.boundaries(0.4, 4), 0.4)              # the list of the run without "control"
-    assert [l[:4] for l in n2.launch_list(span, forcing, mon, None)] == want
-    assert all(l[4] is None for l in n2.launch_list(span, forcing, mon, None))
+    # the list of the run without "control": output times 0.1 .. 0.4, the breakpoint 0.13, samples half way and at the ends
+    want = [(0.0, 0.05, None, 1), (0.05, 0.1, 1, 2), (0.1, 0.13, None, None), (0.13, 0.15000000000000002, None, 3),
+            (0.15000000000000002, 0.2, 2, 4), (0.2, 0.25, None, 5), (0.25, 0.30000000000000004, 3, 6),
+            (0.30000000000000004, 0.35000000000000003, None, 7), (0.35000000000000003, 0.4, 4, 8)]
+    L = launches.merge(0.4, 4, sched.times, mon.times, None)[0]
+    assert [l[:4] for l in L] == want
+    assert all(l.control is None for l in L)
     plain = [(float(span[i]), float(span[i + 1]), i + 1, None, None) for i in range(4)]
-    assert n2.launch_list(span) == plain
+    assert launches.merge(0.4, 4)[0] == plain
     # the code object of an uncontrolled run: same plan, same cache key as before the controller existed
     mech = plan.Mechanism(mi)
     row = plan.member_constants(mi, mech, 20)[1]

@@ -909,7 +909,7 @@ def test_single_process_and_multi_rank_routes_load_the_same_code_object(case, mo
     (cache key, hipRTC options).  The members differ in one column, so literals are in play; geometry and defines
     are chosen per `ivp` as run_dynamic does."""
     import copy
-    from rmt_app_amd import n2, schedule
+    from rmt_app_amd import launches, n2, schedule
     from rmt_app_amd.ensemble import expand_members
     _, make, ivp, E, N, forced, geometry = case
     base = make(ivp=ivp)
@@ -937,7 +937,8 @@ def test_single_process_and_multi_rank_routes_load_the_same_code_object(case, mo
 
     def forcing():
         sched = schedule.parse(base, inputs, ivp)
-        return n2.Forcing(sched, base["operating-conditions"]["period"], 2, N) if forced else None
+        return n2.Forcing(sched, launches.merge(base["operating-conditions"]["period"], 2, sched.times)[0], N) \
+            if forced else None
     # the single-process route: the rows open_members packs for one process, through precompile
     pairs = [pack(mi, mech, N) for mi in inputs]
     rows = np.array([r for _, r in pairs])

@@ -16,7 +16,7 @@ import torch
 
 import emu_device
 import inputs as INP
-from rmt_app_amd import hipbind, isa, monitor, plan, rmtExe, schedule
+from rmt_app_amd import hipbind, isa, launches, monitor, plan, rmtExe, schedule
 from rmt_app_amd import m2 as M2
 from rmt_app_amd import n2
 
@@ -104,36 +104,40 @@ def test_samples_per_interval():
     want = np.concatenate([[0.0], np.linspace(out[0], out[1], 4)[1:], np.linspace(out[1], out[2], 4)[1:]])
     assert mon.K == 7 and np.array_equal(mon.times, want)
     assert mon.times[3] == out[1] and mon.times[6] == out[2]     # every output time is a sample
-    L = mon.refine(plain(0.5, 2), 0.5)
-    assert [(k, s) for _, _, k, s in L] == [(None, 1), (None, 2), (1, 3), (None, 4), (None, 5), (2, 6)]
-    assert [a for a, _, _, _ in L] == list(mon.times[:-1]) and [b for _, b, _, _ in L] == list(mon.times[1:])
+    L, times, _ = launches.merge(0.5, 2, (), mon.times)
+    assert [(l.out, l.sample) for l in L] == [(None, 1), (None, 2), (1, 3), (None, 4), (None, 5), (2, 6)]
+    assert [l.t0 for l in L] == list(mon.times[:-1]) and [l.t1 for l in L] == list(mon.times[1:])
+    assert np.array_equal(times, mon.times) and all(l.control is None for l in L)
     # the launches ARE those of an unmonitored run with six output times
-    assert [(a, b) for a, b, _, _ in L] == [(a, b) for a, b, _ in plain(0.5, 6)]
+    assert [(l.t0, l.t1) for l in L] == [(a, b) for a, b, _ in plain(0.5, 6)]
+    assert [l[:3] for l in launches.merge(0.5, 6)[0]] == plain(0.5, 6)
 
 
 def test_explicit_times_one_on_an_output_time():
     mon = monitor.parse(_input(times=[0.1, 0.25*(1 + 1e-14), 0.4]), 2)
     assert np.array_equal(mon.times, [0.0, 0.1, 0.25, 0.4])     # the near-output sample IS the output time
-    L = mon.refine(plain(0.5, 2), 0.5)
-    assert L == [(0.0, 0.1, None, 1), (0.1, 0.25, 1, 2), (0.25, 0.4, None, 3), (0.4, 0.5, 2, None)]
+    L = launches.merge(0.5, 2, (), mon.times)[0]
+    assert [l[:4] for l in L] == [(0.0, 0.1, None, 1), (0.1, 0.25, 1, 2), (0.25, 0.4, None, 3), (0.4, 0.5, 2, None)]
     # the period itself may be a sample
     mon = monitor.parse(_input(times=[0.5]), 2)
-    assert mon.refine(plain(0.5, 2), 0.5) == [(0.0, 0.25, 1, None), (0.25, 0.5, 2, 1)]
+    assert [l[:4] for l in launches.merge(0.5, 2, (), mon.times)[0]] == [(0.0, 0.25, 1, None), (0.25, 0.5, 2, 1)]
 
 
 def test_breakpoints_samples_and_outputs_merge_without_duplicates():
     mi = _input(times=[0.1, 0.2*(1 - 1e-13), 0.25, 0.3])
     mi["solver-config"]["schedule"] = {"time": [0.0, 0.2, 0.2, 0.35, 0.5], "inlet-temperature": [523, 523, 533, 533, 533]}
     sched = schedule.parse(mi, None, "hip-rk45")
-    base = sched.boundaries(0.5, 2)
-    assert base == [(0.0, 0.2, None), (0.2, 0.25, 1), (0.25, 0.35, None), (0.35, 0.5, 2)]
+    base = launches.merge(0.5, 2, sched.times)[0]
+    assert [l[:3] for l in base] == [(0.0, 0.2, None), (0.2, 0.25, 1), (0.25, 0.35, None), (0.35, 0.5, 2)]
     mon = monitor.parse(mi, 2)
-    L = mon.refine(base, 0.5)
-    assert L == [(0.0, 0.1, None, 1), (0.1, 0.2, None, 2), (0.2, 0.25, 1, 3), (0.25, 0.3, None, 4), (0.3, 0.35, None, None),
-                 (0.35, 0.5, 2, None)]
-    assert mon.times[2] == 0.2                                   # the sample at the jump IS the breakpoint
-    ends = [b for _, b, _, _ in L]
-    assert len(set(ends)) == len(ends) and all(b > a for a, b, _, _ in L)
+    given = mon.times.copy()
+    L, times, _ = launches.merge(0.5, 2, sched.times, mon.times)
+    assert [l[:4] for l in L] == [(0.0, 0.1, None, 1), (0.1, 0.2, None, 2), (0.2, 0.25, 1, 3), (0.25, 0.3, None, 4),
+                                  (0.3, 0.35, None, None), (0.35, 0.5, 2, None)]
+    assert times[2] == 0.2 and given[2] != 0.2                   # the sample at the jump IS the breakpoint
+    assert np.array_equal(mon.times, given)                      # (in the returned copy: the argument is left alone)
+    ends = [l.t1 for l in L]
+    assert len(set(ends)) == len(ends) and all(l.t1 > l.t0 for l in L)
 
 
 # ----------------------------------------------------------------------------- conversion
@@ -291,7 +295,7 @@ def check_against_fine(mon, coarse, fine, model="N2", xs=None):
 def test_emulated_run_equals_the_fine_unmonitored_run(model):
     del MONITOR_CALLS[:]
     a = _emu_run(_emu_input(model, 2, {"samples": 3}))
-    assert len(MONITOR_CALLS) == 7 and "monitor-raw" not in a["device-stats"]
+    assert len(MONITOR_CALLS) == 7 and not any(k.endswith("raw") for k in a["device-stats"])
     b = _emu_run(_emu_input(model, 6))
     assert "monitor" not in b and len(MONITOR_CALLS) == 7          # without the key nothing is monitored
     xs = np.linspace(0, INP.m2_dme_input()["reactor"]["ReLe"], 48)

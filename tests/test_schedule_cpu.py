@@ -12,7 +12,7 @@ import pytest
 import inputs as INP
 from oracle import n2_oracle as O
 from oracle.hostemu import HostEmu
-from rmt_app_amd import hipbind, isa, n2, plan, rmtExe, schedule
+from rmt_app_amd import hipbind, isa, launches, n2, plan, rmtExe, schedule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
@@ -61,12 +61,12 @@ def test_piecewise_linear_jumps_and_holds():
 
 def test_launch_boundaries_and_pieces():
     s = schedule.parse(with_schedule(STEP))
-    b = s.boundaries(0.5, 2)                  # outputs 0.25, 0.5; breakpoints 0.1, 0.2 inside
-    assert [(round(a, 12), round(c, 12), k) for a, c, k in b] == [
+    b = launches.merge(0.5, 2, s.times)[0]    # outputs 0.25, 0.5; breakpoints 0.1, 0.2 inside
+    assert [(round(l.t0, 12), round(l.t1, 12), l.out) for l in b] == [
         (0.0, 0.1, None), (0.1, 0.2, None), (0.2, 0.25, 1), (0.25, 0.5, 2)]
     # a breakpoint ON an output time adds no launch, whatever linspace rounds it to
-    b = s.boundaries(0.3, 6)
-    assert len(b) == 6 and [k for _, _, k in b] == [1, 2, 3, 4, 5, 6]
+    b = launches.merge(0.3, 6, s.times)[0]
+    assert len(b) == 6 and [l.out for l in b] == [1, 2, 3, 4, 5, 6]
     v0, sl = s.launch(0.1, 0.2)
     np.testing.assert_allclose(v0[0], [523, 5e6, 523])
     np.testing.assert_allclose(sl[0], [100.0, 0.0, 0.0])
@@ -77,7 +77,7 @@ def test_launch_boundaries_and_pieces():
     np.testing.assert_allclose(v0[0], [528, 4.9e6, 533])
     assert not sl.any()
     # inside one launch the forcing is ONE linear function: start value + slope (t - t0) reproduces at()
-    for a, c, _ in s.boundaries(0.5, 2):
+    for a, c in [l[:2] for l in launches.merge(0.5, 2, s.times)[0]]:
         v0, sl = s.launch(a, c)
         for t in np.linspace(a, c, 5)[:-1]:
             np.testing.assert_allclose(v0 + sl*(t - a), s.at(t), rtol=1e-14)

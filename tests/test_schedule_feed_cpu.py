@@ -13,7 +13,7 @@ import emu_device
 import inputs as INP
 from oracle import n2_oracle as O
 from oracle.hostemu import HostEmu
-from rmt_app_amd import hipbind, isa, n2, plan, rmtExe, schedule
+from rmt_app_amd import hipbind, isa, launches, n2, plan, rmtExe, schedule
 from rmt_app_amd.ensemble import expand_members
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,12 +76,12 @@ def test_shapes_and_piecewise_linear_composition():
     np.testing.assert_allclose(c0[0], FEED, rtol=0)
     assert not cs.any()
     # inside one launch the composition is ONE linear function of t
-    for a, c, _ in s.boundaries(0.4, 2):
+    for a, c in [l[:2] for l in launches.merge(0.4, 2, s.times)[0]]:
         c0, cs = s.conc_launch(a, c)
         for t in np.linspace(a, c, 5)[:-1]:
             np.testing.assert_allclose(c0 + cs*(t - a), s.conc_at(t), rtol=1e-13)
         np.testing.assert_allclose(c0 + cs*(c - a), s.conc_at(c, "left"), rtol=1e-13)
-    assert [k for _, _, k in s.boundaries(0.4, 2)] == [None, 1, None, 2]           # 0.1 | 0.2 | 0.3 | 0.4
+    assert [l.out for l in launches.merge(0.4, 2, s.times)[0]] == [None, 1, None, 2]           # 0.1 | 0.2 | 0.3 | 0.4
 
 
 def test_without_the_key_nothing_is_added():

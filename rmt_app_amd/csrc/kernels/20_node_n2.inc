@@ -1,21 +1,6 @@
 #if RMT_MODEL == 0
 // ------------------------------------------------------------------ node physics
-// Two cuts of the node function's multiplications (each its own switch, default on; profiles/node_cuts.md):
-//  RMT_NODE_CONV_FOLD     the convective term as (F1 inv_dz)(up - y): the product is a per-reactor constant - a literal
-//                         where the member fields are literals (RMT_MC_*), else formed once per call
-//  RMT_NODE_X_FROM_STATE  x_i = cc_i / sum cc from the clamped state itself (C_i = cmax cc_i scales numerator and
-//                         denominator alike), only where the kinetics never read C (RMT_KIN_USES_C 0, from the lowering)
-//                         and the unit has no rmt_node_jac (the stiff stepper differentiates x_i = C_i / sum C as written)
-#ifndef RMT_NODE_CONV_FOLD
-#define RMT_NODE_CONV_FOLD 1
-#endif
-#ifndef RMT_NODE_X_FROM_STATE
-#define RMT_NODE_X_FROM_STATE 1
-#endif
-#ifndef RMT_KIN_USES_C
-#define RMT_KIN_USES_C 1
-#endif
-#define RMT_NODE_X_CC (RMT_NODE_X_FROM_STATE && !RMT_KIN_USES_C && !RMT_WITH_ROS4)
+// (the switches of the node function's cuts and their defaults: 10_member.inc, in front of RmtMember)
 // Phase A (before the pressure scan): clamp, real concentrations, mole fractions, T, mixture MW,
 // Ergun affine coefficient.  pbHomoReactor.py:3897-3928, 3960-3979.
 struct RmtNode {
@@ -24,18 +9,22 @@ struct RmtNode {
     real T, M;
     real invT;     // 1/T: M/T below and every c/T, c/(R T) of the kinetics
     real MoT;      // M/T, shared by the Ergun coefficient and the EOS density
+#if RMT_NODE_CS
+    real ict;      // 1/sum cs; x holds cs, MoT is 1e3 M/T and M is not formed
+#endif
 };
 
-__device__ __forceinline__ preal rmt_node_pre(const RmtMember& m, const real* __restrict__ ys,
-                                              RmtNode& nd) {
-    real ctot = real(0);
+// rmt_node_pre in two halves around its reciprocal, so that rmt_rhs_block can take the reciprocals of a lane's two nodes
+// from one (RMT_NODE_PAIR_RCP): _sum returns sum(state) * T, _fin takes its reciprocal.
+__device__ __forceinline__ real rmt_node_pre_sum(const RmtMember& m, const real* __restrict__ ys, RmtNode& nd,
+                                                 real& ctot) {
+    ctot = real(0);
 #if RMT_NODE_X_CC
-    real cs[RMT_S];                                       // ctot, inv_ctot below: of the clamped state (no cmax)
 #pragma unroll
-    for (int i = 0; i < RMT_S; ++i) {
-        cs[i] = rmt_max(ys[i], RMT_EPS);                  // :3899
-        nd.C[i] = cs[i] * m.cmax;                         // :3903 (MAX scaling; no reader here: removed)
-        ctot += cs[i];
+    for (int i = 0; i < RMT_S; ++i) {                     // ctot, inv_ctot below: of the clamped state (no cmax)
+        nd.x[i] = rmt_max(ys[i], RMT_EPS);                // :3899 (cs_i; scaled to x_i in _fin unless RMT_NODE_CS)
+        nd.C[i] = nd.x[i] * m.cmax;                       // :3903 (MAX scaling; no reader here: removed)
+        ctot += nd.x[i];
     }
 #else
 #pragma unroll
@@ -50,24 +39,40 @@ __device__ __forceinline__ preal rmt_node_pre(const RmtMember& m, const real* __
 #else
     nd.T = ys[RMT_S] * m.tf + m.tf;                       // :3914
 #endif
-    // 1/sum(C) and 1/T from ONE reciprocal of their product (v_rcp_f64 issues at a quarter of the FMA rate and each
-    // reciprocal carries two Newton steps: 3 multiplications instead of a second one; both factors are O(1)..O(1e3))
+    return ctot * nd.T;
+}
+
 #ifndef RMT_NODE_RCP_MERGE
 #define RMT_NODE_RCP_MERGE 1
 #endif
+__device__ __forceinline__ preal rmt_node_pre_fin(const RmtMember& m, RmtNode& nd, const real ctot, const real inv_ct_T) {
+    // 1/sum(C) and 1/T from ONE reciprocal of their product (v_rcp_f64 issues at a quarter of the FMA rate and each
+    // reciprocal carries two Newton steps: 3 multiplications instead of a second one; both factors are O(1)..O(1e3))
 #if RMT_NODE_RCP_MERGE
-    const real inv_ct_T = rmt_rcp(ctot * nd.T);
     const real inv_ctot = inv_ct_T * nd.T;
     nd.invT = inv_ct_T * ctot;
+    const real ict_T = inv_ct_T;
 #else
+    (void)inv_ct_T;
     const real inv_ctot = rmt_rcp(ctot);
     nd.invT = rmt_rcp(nd.T);
+    const real ict_T = inv_ctot * nd.invT;
 #endif
+    (void)ict_T;
     real mw = real(0);
+#if RMT_NODE_CS
+    nd.ict = inv_ctot;
+#pragma unroll
+    for (int i = 0; i < RMT_S; ++i) mw += nd.x[i] * RMT_MW[i];
+    nd.M = real(0);
+    const preal mot = preal(mw) * preal(ict_T);           // 1e3 M/T
+    nd.MoT = real(mot);
+    return preal(1) - m.alpha_k * mot;                    // (alpha_k carries the 1e-3: rmt_load_member)
+#else
 #pragma unroll
     for (int i = 0; i < RMT_S; ++i) {
 #if RMT_NODE_X_CC
-        nd.x[i] = cs[i] * inv_ctot;                       // :3927
+        nd.x[i] = nd.x[i] * inv_ctot;                     // :3927
 #else
         nd.x[i] = nd.C[i] * inv_ctot;                     // :3927
 #endif
@@ -78,6 +83,18 @@ __device__ __forceinline__ preal rmt_node_pre(const RmtMember& m, const real* __
     const preal mot = preal(nd.M) * preal(nd.invT);
     nd.MoT = real(mot);
     return preal(1) - m.alpha_k * mot;
+#endif
+}
+
+__device__ __forceinline__ preal rmt_node_pre(const RmtMember& m, const real* __restrict__ ys,
+                                              RmtNode& nd) {
+    real ctot;
+    const real ct_T = rmt_node_pre_sum(m, ys, nd, ctot);
+#if RMT_NODE_RCP_MERGE
+    return rmt_node_pre_fin(m, nd, ctot, rmt_rcp(ct_T));
+#else
+    return rmt_node_pre_fin(m, nd, ctot, real(0));
+#endif
 }
 
 // Phase B (pressure known): kinetics, species source, Cp, heat of reaction, wall exchange,
@@ -88,14 +105,28 @@ __device__ __forceinline__ void rmt_node_post(const RmtMember& m, const RmtNode&
                                               const real* __restrict__ up, const preal Pz,
                                               real* __restrict__ k, FL& flag, const real* __restrict__ rin = nullptr,
                                               KC* kc = nullptr) {
+    // A caller with a cache gets the unit's rmt_kinetics_node where there is one (plan.Mechanism.node_kinetics: literal
+    // prefactors and FM inside the cached constants, the gain's reciprocal from the rate laws' division group); a caller
+    // without one the plain rmt_kinetics - the plain twin of a caching stepper returns bit for bit what a cache-less
+    // build of the same geometry returns.
+    constexpr bool KNODE = KC::enabled && !HAVE_R && (RMT_KIN_NODE != 0);
+    constexpr bool FMR = KNODE && (RMT_KIN_RATES_FM != 0);        // the rates arrive scaled by FM
+    constexpr bool GDEN = KNODE && (RMT_KIN_GAIN_DEN != 0);       // 1/gden comes back from the rate function
+#if RMT_NODE_CS
+    const real P = real(Pz) * nd.ict;                     // P / sum cs: with x := cs the partial pressures are x_i P as before
+#else
     const real P = real(Pz);
+#endif
     // (1) convective parts first: after this the stage state and the upstream values are dead,
     //     which keeps the register footprint of the kinetics small.
 #if RMT_NODE_CONV_FOLD
     const real conv = m.f1 * m.inv_dz;
 #pragma unroll
-    for (int i = 0; i < RMT_S; ++i)
-        k[i] = conv * (up[i] - ys[i]);                                  // :4086-4098, convective term
+    for (int i = 0; i < RMT_S; ++i) {
+        // FMR: only the difference now, k_i = conv (up_i - y_i) + src_i in one fma behind the rates
+        if constexpr (FMR) k[i] = up[i] - ys[i];
+        else k[i] = conv * (up[i] - ys[i]);                             // :4086-4098, convective term
+    }
 #else
 #pragma unroll
     for (int i = 0; i < RMT_S; ++i)
@@ -123,10 +154,14 @@ __device__ __forceinline__ void rmt_node_post(const RmtMember& m, const RmtNode&
 #pragma unroll
         for (int q = 0; q < RMT_R; ++q) hq[q] = dcp[q] * (T - RMT_TREF) + RMT_DH25[q];   // :4025-4028
     }
-    const real qm = (m.tm == real(0)) ? real(0) : m.ua * (m.tm - T);    // rmtUtility.py:438-445
+    const real qm = (m.tm == real(0)) ? real(0) : (FMR ? m.qm_kf : m.ua) * (m.tm - T);    // rmtUtility.py:438-445
     // const_T2/GaHeCoTe0 (:4077, 4118) = F1/(GaHeCoTe0 rho* Cp*), rho* = P M/(R T GaDe0) (:3964-3966),
-    // Cp* = Cp/Cp0 (:4016): the four per-reactor constants arrive as ONE (member field GAIN_K)
-    const real gain = m.inv_hecote * rmt_rcp((P * nd.MoT) * cpm);
+    // Cp* = Cp/Cp0 (:4016): the four per-reactor constants arrive as ONE (member field GAIN_K; m.gain_k / gain_kf: with the
+    // factors of the cuts, rmt_load_member).  RMT_NODE_CS: P is P / sum cs, MoT is 1e3 M/T and cpm is sum cs_i cpbar_i -
+    // the product is 1e3 times the plain one
+    const real gden = (P * nd.MoT) * cpm;
+    real ginv = real(0);
+    if constexpr (!GDEN) ginv = rmt_rcp(gden);
 #endif
     // (3) kinetics and the source terms
     real r[RMT_R];
@@ -135,7 +170,21 @@ __device__ __forceinline__ void rmt_node_post(const RmtMember& m, const RmtNode&
         for (int q = 0; q < RMT_R; ++q) r[q] = rin[q];
     } else {
         if constexpr (KC::enabled) {      // :3989-3992; KMODE 2: the temperature-only constants from the node's cache
+#if RMT_KIN_NODE
+#if RMT_KIN_RATES_FM
+#define RMT_KIN_NODE_FM , m.inv_macote
+#else
+#define RMT_KIN_NODE_FM
+#endif
+#if RMT_KIN_GAIN_DEN
+            rmt_kinetics_node<FL, KC, KMODE>(nd.T, nd.invT, P, nd.x, nd.C, m.user, r, flag, *kc RMT_KIN_NODE_FM, gden, ginv);
+#else
+            rmt_kinetics_node<FL, KC, KMODE>(nd.T, nd.invT, P, nd.x, nd.C, m.user, r, flag, *kc RMT_KIN_NODE_FM);
+#endif
+#undef RMT_KIN_NODE_FM
+#else
             rmt_kinetics<FL, KC, KMODE>(nd.T, nd.invT, P, nd.x, nd.C, m.user, r, flag, *kc);
+#endif
         } else {
             rmt_nocache_t nc;
             rmt_kinetics(nd.T, nd.invT, P, nd.x, nd.C, m.user, r, flag, nc);    // :3989-3992
@@ -145,12 +194,21 @@ __device__ __forceinline__ void rmt_node_post(const RmtMember& m, const RmtNode&
     rmt_species_source(r, src);                                         // :4000 (sparse nu^T r)
     const real fm = m.inv_macote;                                       // member field FM = F1/GaMaCoTe0
 #pragma unroll
-    for (int i = 0; i < RMT_S; ++i) k[i] += fm * src[i];                // :4098
+    for (int i = 0; i < RMT_S; ++i) {
+#if RMT_NODE_CONV_FOLD
+        if constexpr (FMR) k[i] = conv * k[i] + src[i];                 // :4086-4098 (src carries FM)
+        else k[i] += fm * src[i];                                       // :4098
+#else
+        if constexpr (FMR) k[i] += src[i];
+        else k[i] += fm * src[i];
+#endif
+    }
 #if !RMT_ISO
+    const real gain = (FMR ? m.gain_kf : m.gain_k) * ginv;
     real qr = real(0);
 #pragma unroll
     for (int q = 0; q < RMT_R; ++q) qr += r[q] * hq[q];                 // :4032
-    k[RMT_S] += gain * (qm - qr);                                       // :4118-4126
+    k[RMT_S] += gain * (qm - qr);                                       // :4118-4126 (FMR: qm and qr carry FM, gain 1/FM)
 #endif
 }
 

@@ -26,9 +26,23 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
     RmtNode nd[NPT];
     RmtAff loc[NPT];
     RmtAff mine = {preal(1), preal(0)};
+    // RMT_NODE_PAIR_RCP (the caching steppers at two nodes per lane): the two nodes' 1/(sum(state) T) from ONE reciprocal
+    // of the product, 3 multiplications instead of the second v_rcp_f64 and its Newton steps.  A lane beyond the
+    // reactor's end carries the inlet state: every factor is positive and O(1)..O(1e3)
+    real pair_ct[NPT], pair_inv[NPT];
+    constexpr bool PAIR = (NPT == 2) && KC::enabled && (RMT_NODE_PAIR_RCP != 0) && (RMT_NODE_RCP_MERGE != 0);
+    if constexpr (PAIR) {
+        const real d0 = rmt_node_pre_sum(m, ys[0], nd[0], pair_ct[0]);
+        const real d1 = rmt_node_pre_sum(m, ys[NPT - 1], nd[NPT - 1], pair_ct[NPT - 1]);
+        const real t = rmt_rcp(d0 * d1);
+        pair_inv[0] = t * d1;
+        pair_inv[NPT - 1] = t * d0;
+    }
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
-        const preal a = rmt_node_pre(m, ys[j], nd[j]);
+        preal a;
+        if constexpr (PAIR) a = rmt_node_pre_fin(m, nd[j], pair_ct[j], pair_inv[j]);
+        else a = rmt_node_pre(m, ys[j], nd[j]);
         loc[j].a = (j < nvalid) ? a : preal(1);
         loc[j].b = (j < nvalid) ? m.beta : preal(0);
         mine = rmt_then(mine, loc[j]);

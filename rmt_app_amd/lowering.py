@@ -737,6 +737,52 @@ class Lowered:
         partial = [{k: v.i for k, v in d[o].items()} for o in self.outputs]
         return Gradient(g2, [new[o].i for o in self.outputs], partial, self.S, n_primal, wrt)
 
+    # ---- homogeneity in (x, P): may the node function hand over the unnormalised composition?
+    def xp_invariant(self):
+        """True when every rate is unchanged under (x, P) -> (lambda x, P/lambda), lambda > 0, and SpCoi is not read: the
+        rates then depend on the composition only through the partial pressures x_i P, and the node function may pass
+        the clamped state for x and P/sum(state) for P without ever forming the mole fractions (csrc/kernels/20_node_n2.inc,
+        RMT_NODE_NO_X).  Degree bookkeeping over the DAG: x_i has degree +1, P degree -1, constants, T and the user
+        parameters degree 0; products and quotients add and subtract degrees, sums (and min / max) need equal degrees,
+        integer powers and square roots scale them, every other function needs degree 0."""
+        from fractions import Fraction
+        g = self.g
+        deg = {}
+        for i in sorted(self.live):
+            op, a, b = g.nodes[i]
+            if op == "const":
+                d = Fraction(0)
+            elif op == "in":
+                if a[0] == "C":
+                    return False
+                d = Fraction(1) if a[0] == "x" else (Fraction(-1) if a == "P" else Fraction(0))
+            elif op == "mul":
+                d = deg[a] + deg[b]
+            elif op == "div":
+                d = deg[a] - deg[b]
+            elif op == "rcp":
+                d = -deg[a]
+            elif op in ("neg", "abs"):
+                d = deg[a]
+            elif op in ("add", "sub", "min", "max"):
+                if deg[a] != deg[b]:
+                    return False
+                d = deg[a]
+            elif op == "powi":
+                d = deg[a]*b
+            elif op == "sqrt":
+                d = deg[a]/2
+            elif op == "pow":
+                if deg[b] != 0 or (deg[a] != 0 and not g.is_const(b)):
+                    return False
+                d = deg[a]*Fraction(g.cval(b)) if g.is_const(b) else Fraction(0)
+            else:                                         # exp, log, trigonometric functions, sign, step, ...
+                if deg[a] != 0:
+                    return False
+                d = Fraction(0)
+            deg[i] = d
+        return all(deg[o] == 0 for o in self.outputs)
+
     # ---- one reciprocal for independent divisions
     DIV_BATCH_CAP = 4
 
@@ -806,11 +852,15 @@ class Lowered:
             for k, n in enumerate(grp):
                 batch[n] = (grp, k)
         inv = {}               # division node -> name of the reciprocal of its denominator
+        extra = getattr(self, "_extra_den", None)         # (denominator, out-parameter) of the caller, see emit
+        extra_done = self._extra_done = []
 
         def group_lines(grp, name):
             """the prefix-product inversion of a group (div_groups), printed at its first division"""
             den = [name[self.denominator(n)] for n in grp]
-            tag, n = "b%d" % grp[0], len(grp)
+            if extra and not extra_done:                  # the caller's own denominator rides along (emit(extra_den=True))
+                den.append(extra[0])
+            tag, n = "b%d" % grp[0], len(den)
             out, prod = [], den[0]
             for k in range(1, n):                         # p_k = d_1 .. d_(k+1)
                 out.append("    const real %s_p%d = %s * %s;" % (tag, k, prod, den[k]))
@@ -823,8 +873,12 @@ class Lowered:
                     out.append("    const real %s_t%d = %s_t%d * %s;" % (tag, k - 1, tag, k, den[k]))
                 else:
                     out.append("    const real %s_i0 = %s_t1 * %s;" % (tag, tag, den[1]))
-                inv[grp[k]] = "%s_i%d" % (tag, k)
+                if k < len(grp):
+                    inv[grp[k]] = "%s_i%d" % (tag, k)
             inv[grp[0]] = "%s_i0" % tag
+            if extra and not extra_done:
+                out.append("    %s = %s_i%d;" % (extra[1], tag, n - 1))
+                extra_done.append(True)
             return out
 
         def lit(v):
@@ -1138,12 +1192,30 @@ class Lowered:
                 "prologue": prologue, "tslot": tslot, "outside_exp": outside}
 
     def emit(self, fname="rmt_kinetics", const_table=False, kcache=False, kcache_gen=True, kcache_thr=None,
-             div_batch=False):
+             div_batch=False, kcache_fold=False, rate_scale=False, extra_den=False, head=True):
         """The device function of the rates.  ``kcache``: with the cached section of kcache_plan() for callers that
         pass a cache (template parameter KC with KC::enabled; every other caller passes rmt_nocache_t and gets the
         plain evaluation - the section is discarded at compile time).  ``div_batch``: independent divisions share one
-        reciprocal (div_groups; plan.Mechanism.source switches it on unless RMT_DIV_BATCH 0 is among its defines)."""
+        reciprocal (div_groups; plan.Mechanism.source switches it on unless RMT_DIV_BATCH 0 is among its defines).
+
+        Three more, for the node function of a caching stepper (plan.Mechanism.source, `rmt_kinetics_node`), each off by
+        default - the text of the calls above does not change:
+        ``kcache_fold``: a literal factor that every consumer of a cached constant multiplies onto it is applied ONCE, in
+        the full evaluation before `kc.put` (K c obeys the same Taylor update as K); the consumer becomes a copy.  Covers
+        a chain of literal factors behind the constant, v19 * (v116 * c), too.  Slots and range tests do not change.
+        ``rate_scale`` (with kcache_fold): one more parameter `const real rscale`; every rate leaves multiplied by it,
+        through one cached constant of the rate's product chain (its literal times rscale goes in before `kc.put`, so the
+        cached evaluations pay nothing; rscale must not change while a cache is in use) - if some rate has no such chain
+        nothing is scaled, there is no such parameter and `self.rates_scaled` is False.
+        ``extra_den``: two more parameters `const real gden, real& ginv` (behind rscale); 1/gden joins the first division group as one
+        more member of its prefix-product inversion (a plain reciprocal where there is no group).  gden must exist before
+        the call and be positive; the product's range is the caller's business."""
         self._const_table = {} if const_table else None
+        self._extra_den = ("gden", "ginv") if extra_den else None
+        self._extra_done = []
+        self._fold = bool(kcache_fold)
+        self._rate_scale = bool(rate_scale)
+        self.rates_scaled = False
         self._div_batch = self.div_groups() if div_batch else None        # (one reciprocal per group, see div_groups)
         plan = self.kcache_plan(kcache_gen) if kcache else None
         self._kc_thr = self.KC_THR
@@ -1157,6 +1229,9 @@ class Lowered:
             lines, name = self._emit_cached(plan)
         table, self._const_table = self._const_table, None
         self._div_batch = None
+        if self._extra_den and not self._extra_done:      # no division group to join
+            lines.insert(0, "    ginv = rmt_rcp(gden);")
+        self._extra_den = None
         body = "\n".join(lines)
         if table:
             vals = sorted(table, key=table.get)
@@ -1166,14 +1241,78 @@ class Lowered:
         else:
             self._table_decl = ""
         outs = "\n".join("    r[%d] = %s;" % (k, name[o]) for k, o in enumerate(self.outputs))
-        head = "#define RMT_KC_SLOTS %d\n" % (plan["slots"] if plan else 0)
+        head = "#define RMT_KC_SLOTS %d\n" % (plan["slots"] if plan else 0) if head else ""
         return head + self._table_decl + (
             "template <typename FL, typename KC, int MODE = 0>\n"
             "__device__ __forceinline__ void %s(const real T, const real invT, const real P,\n"
             "        const real* __restrict__ x, const real* __restrict__ C, const real* __restrict__ U,\n"
-            "        real* __restrict__ r, FL& flag, KC& kc) {\n"
+            "        real* __restrict__ r, FL& flag, KC& kc%s) {\n"
             "    (void)invT; (void)U; (void)kc;\n%s\n%s\n}\n"
-            % (fname, body, outs))
+            % (fname, (", const real rscale" if self.rates_scaled else "") + (", const real gden, real& ginv" if extra_den else ""),
+               body, outs))
+
+    def _fold_plan(self, plan):
+        """emit(kcache_fold=True): ({cached constant: literal applied before kc.put}, {node: node it copies})."""
+        g = self.g
+        users = {}
+        for i in sorted(self.live):
+            op, a, b = g.nodes[i]
+            if op in ("const", "in"):
+                continue
+            users.setdefault(a, []).append(i)
+            if b is not None and op != "powi":
+                users.setdefault(b, []).append(i)
+        for o in self.outputs:
+            users.setdefault(o, []).append(-1)
+        kinds, branch = plan["kind"], set(plan["branch"])
+        cached = [r for r in plan["roots"] if kinds[r] != "log"]
+        scale, copy, scaled = {}, {}, set()
+
+        def literal_of(u, r):
+            """(literal, {node: copied node}) if consumer u multiplies r by a literal, directly or as r * (X * c)"""
+            op, a, b = g.nodes[u]
+            if op != "mul" or a == b or u in branch:
+                return None
+            o = b if a == r else a
+            if g.is_const(o):
+                return g.cval(o), {u: r}
+            oop, oa, ob = g.nodes[o]
+            if oop == "mul" and users.get(o) == [u] and o not in branch and g.is_const(oa) != g.is_const(ob):
+                c, X = (oa, ob) if g.is_const(oa) else (ob, oa)
+                return g.cval(c), {o: X}
+            return None
+        for r in cached:
+            us = users.get(r, [])
+            found = [literal_of(u, r) if u >= 0 else None for u in us]
+            if not found or any(f is None for f in found) or len({f[0] for f in found}) != 1:
+                continue
+            c = found[0][0]
+            if not math.isfinite(c) or c == 0.0:
+                continue
+            scale[r] = c
+            for f in found:
+                copy.update(f[1])
+        if self._rate_scale:
+            def carrier(n):
+                """the cached constant at the end of a chain of single-use products below node n"""
+                if n in cached:
+                    return n
+                op, a, b = g.nodes[n]
+                if op != "mul" or n in branch:
+                    return None
+                for o in (a, b):
+                    if len(users.get(o, [])) == 1 and not g.is_const(o):
+                        r = carrier(o)
+                        if r is not None:
+                            return r
+                return None
+            carriers = [carrier(o) if users.get(o) == [-1] else None for o in self.outputs]
+            if carriers and all(r is not None for r in carriers) and len(set(carriers)) == len(carriers):
+                scaled = set(carriers)
+                for r in carriers:
+                    scale.setdefault(r, 1.0)
+                self.rates_scaled = True
+        return scale, copy, scaled
 
     def _emit_cached(self, plan):
         """Body with the cached section: MODE 2 takes every cached constant from its reference value by a Taylor step
@@ -1185,6 +1324,7 @@ class Lowered:
         g = self.g
         emit = self._emitter()
         lines, name = [], {}
+        scale, copy, scaled = self._fold_plan(plan) if getattr(self, "_fold", False) else ({}, {}, set())
         for i in sorted(self.live):                       # constants and inputs have no code: name them first
             if g.nodes[i][0] in ("const", "in"):
                 emit(i, name)
@@ -1293,6 +1433,11 @@ class Lowered:
                         ln = ln.replace(fn, fn[:-1] + "_sel<KC::enabled>(")
                 L("    " + ln)
             done.add(i)
+            if i in scale:                                    # the literal its consumers would multiply onto it
+                c = "real(%r)" % scale[i]
+                if i in scaled:
+                    c = "rscale" if scale[i] == 1.0 else "(%s * rscale)" % c
+                L("        v%d = v%d * %s;" % (i, i, c))
             if i in plan["slot"]:
                 L("        if constexpr (KC::enabled) {")
                 L("            kc.put(%d, v%d);" % (plan["slot"][i], i))
@@ -1300,9 +1445,14 @@ class Lowered:
                     L("            kc.put(%d, %s);" % (plan["fslot"][i], name[g.nodes[i][1]]))
                 L("        }")
         L("    }")
+        if self.rates_scaled:
+            L("    // (the rates leave scaled by rscale)")
         for i in sorted(self.live):
             if i not in done:
-                lines.extend(emit(i, name))
+                if i in copy:                                 # its literal sits in the cached constant
+                    name[i] = name[copy[i]]
+                else:
+                    lines.extend(emit(i, name))
                 done.add(i)
         return lines, name
 

@@ -174,6 +174,9 @@ class Mechanism:
             # whether the rate expressions read SpCoi at all: where they do not, the node function forms the mole
             # fractions from the scaled state itself (csrc/kernels/20_node_n2.inc, RMT_NODE_X_FROM_STATE)
             "#define RMT_KIN_USES_C %d" % (1 if any(self.device_dag().uses("C%d" % i) for i in range(self.S)) else 0),
+            # whether the rates depend on (x, P) only through the partial pressures x_i P (lowering.Lowered.xp_invariant):
+            # where they do, the node function hands over the clamped state and P / sum(state) (RMT_NODE_NO_X)
+            "#define RMT_KIN_XP_INVARIANT %d" % (1 if self.device_dag().xp_invariant() else 0),
         ] + ([] if (block > 64 or "RMT_EXP_BITS" in (defines or {})) else [
             # one-wave workgroups (small meshes, big ensembles): the 16 KiB exp table would cap the CU
             # at 9 resident waves (measured -30 % at N=20, E=2048); they keep the 64-entry table
@@ -314,6 +317,7 @@ class Mechanism:
                                      kcache_gen=KCACHE_GEN[str((defines or {}).get("RMT_KCACHE_GEN", "1"))],
                                      kcache_thr=(defines or {}).get("RMT_KCACHE_THR"),
                                      div_batch=batch)
+        kin += self.node_kinetics(defines, fp32, with_jac)
         if (defines or {}).get("RMT_WITH_ROS4"):
             # the stiff stepper's node Jacobian is analytic: rates AND their partials by T, x_i, C_i
             kin += self.device_dag().gradient().emit_jac("rmt_kinetics_jac")
@@ -324,6 +328,38 @@ class Mechanism:
             kin += dag.gradient(wrt=wrt).emit_jac("rmt_kinetics_jacp", with_p=True)
         body = template.replace("RMT_KINETICS_SOURCE", kin, 1)
         return self.prelude(fp32, block, npt, lds_state, defines) + body
+
+    def node_kinetics(self, defines, fp32=False, with_jac=False):
+        """`rmt_kinetics_node`: the rate function of the N2 node function (csrc/kernels/20_node_n2.inc) in a unit with the
+        cached section - the same rates as rmt_kinetics with three cuts of the instruction count (profiles/node_cuts.md),
+        each its own switch among the defines, default on ("0" switches it off; with all three off the unit has no such
+        function and rmt_node_post calls rmt_kinetics as before):
+
+          RMT_KC_FOLD        literal prefactors inside the cached constants (lowering.Lowered.emit kcache_fold)
+          RMT_KIN_FOLD_FM    the rates leave scaled by the member field FM = F1/GaMaCoTe0 (rate_scale; needs RMT_KC_FOLD):
+                             a literal of the unit or, read at run time, multiplied in where the reference point moves
+          RMT_KIN_GAIN_RCP   the reciprocal of the heat balance's gain joins the rate laws' division group (extra_den)
+
+        What the function does is announced by macros in front of it: RMT_KIN_NODE, RMT_KIN_RATES_FM, RMT_KIN_GAIN_DEN.
+        Only callers with a cache use the function (rmt_node_post): the plain twin of a caching stepper keeps rmt_kinetics.
+        Not in units that also print a gradient DAG, in fp32 or with RMT_FAST_MATH 0 (the rule of the division pass)."""
+        d = defines or {}
+        on = lambda k: str(d.get(k, "1")) != "0"
+        cached = str(d.get("RMT_KCACHE", "0")) == "1" or str(d.get("RMT_KCACHE_CHAIN", "0")) == "1"
+        if not cached or with_jac or fp32 or not on("RMT_FAST_MATH") or self.model != "N2" or self.steady \
+                or d.get("RMT_KINETICS_KTAB"):
+            return ""
+        fold, gain = on("RMT_KC_FOLD"), on("RMT_KIN_GAIN_RCP") and on("RMT_DIV_BATCH") and not self.iso
+        fm = fold and on("RMT_KIN_FOLD_FM")
+        if not (fold or gain):
+            return ""
+        dag = self.device_dag()
+        text = dag.emit("rmt_kinetics_node", const_table=bool(d.get("RMT_KINETICS_KTAB")), kcache=True,
+                        kcache_gen=KCACHE_GEN[str(d.get("RMT_KCACHE_GEN", "1"))], kcache_thr=d.get("RMT_KCACHE_THR"),
+                        div_batch=on("RMT_DIV_BATCH"), kcache_fold=fold, rate_scale=fm,
+                        extra_den=gain, head=False)
+        return ("#define RMT_KIN_NODE 1\n#define RMT_KIN_RATES_FM %d\n#define RMT_KIN_GAIN_DEN %d\n"
+                % (1 if dag.rates_scaled else 0, 1 if gain else 0)) + text
 
     @property
     def row_width(self):

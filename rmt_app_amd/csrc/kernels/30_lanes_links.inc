@@ -64,18 +64,13 @@ struct RmtKC {
     __device__ __forceinline__ void leave(const bool out) { valid = valid && !out; }     // (sticky, see rmt_rk4_reg_body)
 };
 
-// ------------------------------------------------------------------ affine maps P -> a*P + b
-struct RmtAff { preal a, b; };
-__device__ __forceinline__ RmtAff rmt_then(const RmtAff first, const RmtAff second) {
-    RmtAff o;
-    o.a = second.a * first.a;
-    o.b = second.a * first.b + second.b;
-    return o;
-}
-
 struct RmtShared {
-    preal tot_a[2][RMT_NW];
+#if RMT_NW > 1
+    alignas(16) RmtAff tot[2][RMT_NW];   // a wave's total {a, b}: one 16-byte record (25_prefix.inc)
+#else
+    preal tot_a[2][RMT_NW];              // one wave: there is no cross-wave prefix, and the unit's layout stays what it was
     preal tot_b[2][RMT_NW];
+#endif
     real bnd[2][RMT_NW][RMT_V];
     real red[2][RMT_NW];
     double cin[2][RMT_V + 1];     // chained workgroups: upstream record (up[V], P) of this stage
@@ -84,54 +79,45 @@ struct RmtShared {
                                      // (carry or the upstream chunk's iterate), row w + 1 = last lane of wave w
     real inlet[RMT_V];            // single-workgroup stepper: the inlet values seen by node 0 (written once)
     int abort[2];
+    // wave `wave` leaves its total / p pushed through the total of wave `wave`
+    __device__ __forceinline__ void put_total(const int buf, const int wave, const RmtAff& t) {
+#if RMT_NW > 1
+        tot[buf][wave] = t;
+#else
+        tot_a[buf][wave] = t.a;
+        tot_b[buf][wave] = t.b;
+#endif
+    }
+    __device__ __forceinline__ preal through(const int buf, const int wave, const preal p) const {
+#if RMT_NW > 1
+        return tot[buf][wave].a * p + tot[buf][wave].b;
+#else
+        return tot_a[buf][wave] * p + tot_b[buf][wave];
+#endif
+    }
 };
 
-// pressure entering wave `wave` = p pushed through the totals of the waves before it; branch-free
-// (as a loop over the per-lane value threadIdx.x>>6 the compiler builds an exec-mask loop; mode 2
-// makes the trip count wave-uniform, mode 1 is branch-free and unrolled, mode 0 the plain loop)
-#ifndef RMT_PREFIX_MODE
-#define RMT_PREFIX_MODE 2
-#endif
+// pressure entering wave `wave` = p pushed through the totals of the waves before it, and the pressure leaving the
+// block from the one entering wave `wave` (25_prefix.inc)
 __device__ __forceinline__ preal rmt_push_before(const RmtShared& sh, const int buf, const int wave, preal p) {
-#if RMT_PREFIX_MODE == 1
-#pragma unroll
-    for (int w = 0; w < RMT_NW - 1; ++w) {
-        const preal nx = sh.tot_a[buf][w] * p + sh.tot_b[buf][w];
-        p = (w < wave) ? nx : p;
-    }
-#elif RMT_PREFIX_MODE == 2
-    const int wu = __builtin_amdgcn_readfirstlane(wave);         // wave-uniform trip count: scalar loop
-    for (int w = 0; w < wu; ++w) p = sh.tot_a[buf][w] * p + sh.tot_b[buf][w];
-#elif RMT_PREFIX_MODE == 3
-    // all totals fetched by independent LDS reads (one round trip instead of `wave` dependent ones), then
-    // the short dependent fma chain behind wave-uniform branches
-    const int wu = __builtin_amdgcn_readfirstlane(wave);
-    preal ta[RMT_NW], tb[RMT_NW];
-#pragma unroll
-    for (int w = 0; w < RMT_NW - 1; ++w) { ta[w] = sh.tot_a[buf][w]; tb[w] = sh.tot_b[buf][w]; }
-#pragma unroll
-    for (int w = 0; w < RMT_NW - 1; ++w) {
-        if (w < wu) p = ta[w] * p + tb[w];
-    }
-#else
-    for (int w = 0; w < wave; ++w) p = sh.tot_a[buf][w] * p + sh.tot_b[buf][w];
-#endif
+#ifdef RMT_TIMING_NO_PUSH                  // timing experiments only: results are wrong with it
     return p;
+#elif RMT_NW > 1
+    return rmt_prefix_before<RMT_PREFIX_MODE>(sh.tot[buf], wave, p);
+#else                                     // one wave: the unit's code stays what it was (the scalar loop of mode 2)
+    const int wu = __builtin_amdgcn_readfirstlane(wave);
+    for (int w = 0; w < wu; ++w) p = sh.through(buf, w, p);
+    return p;
+#endif
 }
 __device__ __forceinline__ preal rmt_push_from(const RmtShared& sh, const int buf, const int wave, preal p) {
-#if RMT_PREFIX_MODE == 1
-#pragma unroll
-    for (int w = 0; w < RMT_NW; ++w) {
-        const preal nx = sh.tot_a[buf][w] * p + sh.tot_b[buf][w];
-        p = (w >= wave) ? nx : p;
-    }
-#elif RMT_PREFIX_MODE == 2
-    const int wu = __builtin_amdgcn_readfirstlane(wave);
-    for (int w = wu; w < RMT_NW; ++w) p = sh.tot_a[buf][w] * p + sh.tot_b[buf][w];
+#if RMT_NW > 1
+    return rmt_prefix_from<RMT_PREFIX_MODE>(sh.tot[buf], wave, p);
 #else
-    for (int w = wave; w < RMT_NW; ++w) p = sh.tot_a[buf][w] * p + sh.tot_b[buf][w];
-#endif
+    const int wu = __builtin_amdgcn_readfirstlane(wave);
+    for (int w = wu; w < RMT_NW; ++w) p = sh.through(buf, w, p);
     return p;
+#endif
 }
 
 // ---- chained workgroups (one reactor spread over C workgroups) --------------------------------

@@ -91,8 +91,7 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
     last[RMT_S] = ys[NPT - 1][RMT_S];                                                // :4111
 #endif
     if (lane == 63) {
-        sh.tot_a[buf][wave] = inc.a;
-        sh.tot_b[buf][wave] = inc.b;
+        sh.put_total(buf, wave, inc);
 #pragma unroll
         for (int i = 0; i < RMT_V; ++i) sh.bnd[buf][wave][i] = last[i];
     }
@@ -190,7 +189,7 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
                     }
                     ctx->known = (unsigned)__shfl((int)got, 0);
                 }
-                const preal pe = sh.tot_a[buf][wave] * pw + sh.tot_b[buf][wave];
+                const preal pe = sh.through(buf, wave, pw);
                 if (lane <= RMT_V)
                     sh.cst[buf][lane] = (lane == RMT_V) ? (double)pe : (double)sh.bnd[buf][RMT_NW - 1][lane < RMT_V ? lane : 0];
                 rmt_link_send(rmt_ring_entry(ctx->ring_out, ctx->seq_out), ctx->seq_out, sh.cst[buf], RMT_V + 1);
@@ -259,7 +258,7 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
     }
     if (CHAIN == 1) {
         if (wave == RMT_NW - 1 && rmt_chain_publishes(ctx)) {        // publish this stage's record
-            const preal pe = sh.tot_a[buf][wave] * pw + sh.tot_b[buf][wave];
+            const preal pe = sh.through(buf, wave, pw);
             if (lane <= RMT_V) {                  // sc1 (write-through) stores, drained before the flag
                 const double v = (lane == RMT_V) ? (double)pe : (double)sh.bnd[buf][RMT_NW - 1][lane < RMT_V ? lane : 0];
                 __hip_atomic_store((unsigned long long*)ctx->slots_out +
@@ -418,8 +417,7 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
         const RmtAff inc = rmt_wave_scan(mine);
         if (it > 0) __syncthreads();              // the previous sweep's totals have been read
         if (lane == 63) {
-            sh.tot_a[buf][wave] = inc.a;
-            sh.tot_b[buf][wave] = inc.b;
+            sh.put_total(buf, wave, inc);
         }
         RmtAff exc;
         exc.a = rmt_lane_up1(inc.a);
@@ -466,7 +464,7 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
                     }
                     ctx->known = (unsigned)__shfl((int)got, 0);
                 }
-                const preal pe = sh.tot_a[buf][wave] * pw + sh.tot_b[buf][wave];
+                const preal pe = sh.through(buf, wave, pw);
                 if (lane <= RMT_V)
                     sh.cst[buf][lane] = (lane == RMT_V) ? (double)pe : (double)sh.bnd[buf][RMT_NW - 1][lane < RMT_V ? lane : 0];
                 rmt_link_send(rmt_ring_entry(ctx->ring_out, ctx->seq_out), ctx->seq_out, sh.cst[buf], RMT_V + 1);
@@ -520,7 +518,7 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
     }
     if (CHAIN == 1) {
         if (wave == RMT_NW - 1 && rmt_chain_publishes(ctx)) {        // publish this stage's record
-            const preal pe = sh.tot_a[buf][wave] * pw + sh.tot_b[buf][wave];
+            const preal pe = sh.through(buf, wave, pw);
             if (lane <= RMT_V) {                  // sc1 (write-through) stores, drained before the flag
                 const double v = (lane == RMT_V) ? (double)pe : (double)sh.bnd[buf][RMT_NW - 1][lane < RMT_V ? lane : 0];
                 __hip_atomic_store((unsigned long long*)ctx->slots_out +

@@ -190,8 +190,7 @@ __device__ __forceinline__ void rmt_rhs_block_q(const RmtMember& m, RmtShared& s
     last[RMT_S] = ys[RMT_S];                                                          // :4111
 #endif
     if (lane == 63) {
-        sh.tot_a[buf][wave] = inc.a;
-        sh.tot_b[buf][wave] = inc.b;
+        sh.put_total(buf, wave, inc);
 #pragma unroll
         for (int i = 0; i < RMT_V; ++i) sh.bnd[buf][wave][i] = last[i];
     }
@@ -229,7 +228,7 @@ __device__ __forceinline__ void rmt_rhs_block_q(const RmtMember& m, RmtShared& s
         if (ctx->has_out) {                       // the record for the downstream chunk is complete: send it ahead of the node functions
             if (wave == RMT_QNW - 1 &&
                 !(ctx->chunk == RMT_CHAIN_TEST_STALL_CHUNK && ctx->seq_out >= (unsigned)RMT_CHAIN_TEST_STALL_FROM)) {
-                const preal pe = sh.tot_a[buf][wave] * pw + sh.tot_b[buf][wave];
+                const preal pe = sh.through(buf, wave, pw);
                 if (lane <= RMT_V)
                     sh.cst[buf][lane] = (lane == RMT_V) ? (double)pe : (double)sh.bnd[buf][RMT_QNW - 1][lane < RMT_V ? lane : 0];
                 rmt_link_send(rmt_ring_entry(ctx->ring_out, ctx->seq_out), ctx->seq_out, sh.cst[buf], RMT_V + 1);

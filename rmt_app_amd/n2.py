@@ -263,6 +263,13 @@ def code_plan(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None,
     # unrolled VxV linear algebra is most of the JIT time, so they are compiled on demand
     for f in features:
         defs[FEATURE_DEFINES[f]] = "1"
+    # the cross-wave part of the pressure scan (csrc/kernels/25_prefix.inc): the batched form where it was timed - the unit
+    # of the caching one-workgroup RK4 stepper of model N2 at 512 x 2, built for nothing else (the bench unit; the same
+    # condition as compile_options' register-pressure trackers).  The RK45 unit of that geometry, units with an optional
+    # kernel family and every other geometry keep the template's default, the scalar loop (profiles/prefix_chain.md)
+    if "RMT_PREFIX_MODE" not in defs and str(defs.get("RMT_KCACHE", "0")) == "1" and (block, npt) == (512, 2) \
+            and not features and "RMT_RK45_LDS" not in defs and not fp32 and getattr(mech, "model", "N2") == "N2":
+        defs["RMT_PREFIX_MODE"] = "4"
     if "ros4" in features and "RMT_ROS_QUAD" not in defs and ros4_quad(mech, fp32) and npt == 1:
         defs["RMT_ROS_QUAD"] = "1"            # wide mechanism: one node on four lanes (N2Device tells the C library)
     if getattr(mech, "model", "N2") == "M2" and "RMT_M2_NEWTON" not in defs and rows is not None and newton:

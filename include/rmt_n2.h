@@ -182,6 +182,19 @@ int rmt_n2_ros4(rmt_n2_handle* h, void* y_inout, double t0, double t1, double rt
  * [E][nout][V1] scaled states, V1 = S+2 (M7) or S+3 (M1). */
 int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* out, int nout, double rtol,
                    double atol, double h0, int64_t max_steps, rmt_n2_stats* stats_out);
+/* Steady state of model N2 (solver-config "initial": "steady"): y_out DEVICE double [E][V][N] receives, per member, the
+ * state with f(y) = 0 for the member's rows as they are on the device (a forced row: its values at the row's reference
+ * time).  The discrete steady state is block lower-bidiagonal (first-order upwind, downstream Ergun recurrence), so one
+ * lane marches one reactor from the inlet and solves a V x V system per node by pseudo-transient continuation with the
+ * analytic node Jacobian (csrc/kernels/71_steady_march.inc).  A node is converged when its scaled residual
+ * max_i |f_i| / (F1 (N-1) max(|y_i|, 1e-6)) is at most `tol` and so is its last relative update (or three updates in a
+ * row are, at steps no shorter than the cell's residence time: the residual is at the noise of its evaluation); `max_iter`
+ * bounds the pseudo-time steps per node.  Enqueues ONE kernel on the handle's stream and does not synchronise; needs a code object
+ * generated with RMT_WITH_MARCH (fp64, model N2), else it returns an error.  stats_out DEVICE [E]: t_end = the worst
+ * node's scaled residual, h_last = the node that failed (-1: none), accepted = the largest per-node step count,
+ * rejected = the number of nodes that needed a rejected step.  A member whose march fails (a node at max_iter, a
+ * non-finite state, a zero pivot) gets RMT_N2_FLAG_STEP / RMT_N2_FLAG_NONFINITE and keeps the input downstream of it. */
+int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, int64_t max_iter, rmt_n2_stats* stats_out);
 /* copies the E flag words to host memory (synchronises the stream) and clears them on device */
 int rmt_n2_status(rmt_n2_handle* h, uint32_t* flags_host);
 /* which stepper rmt_n2_rk4 / rk45 / ros4 use: 0 = auto (on-chip if N fits one workgroup, else chained

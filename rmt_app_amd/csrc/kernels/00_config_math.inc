@@ -48,6 +48,11 @@
 #ifndef RMT_WITH_N1
 #define RMT_WITH_N1 0
 #endif
+// RMT_WITH_MARCH: the steady-state march of model N2 (71_steady_march.inc, solver-config "initial"); brings the analytic
+// node Jacobian of the stiff stepper (rmt_node_jac, rmt_kinetics_jac) without the stiff stepper's kernels
+#ifndef RMT_WITH_MARCH
+#define RMT_WITH_MARCH 0
+#endif
 // stiff stepper with ONE NODE ON FOUR LANES (61_ros4_quad.inc): set by the host for mechanisms wider than 8 variables
 #ifndef RMT_ROS_QUAD
 #define RMT_ROS_QUAD 0
@@ -509,4 +514,29 @@ __device__ __forceinline__ float rmt_log2(float x) { return log2f(x); }
 __device__ __forceinline__ float rmt_log10(float x) { return log10f(x); }
 __device__ __forceinline__ float rmt_sqrt(float x) { return sqrtf(x); }
 #endif
+
+// ---- dense inverse of a small matrix, in place (Gauss-Jordan without pivoting; returns the smallest |pivot|: 0 or NaN =
+// singular).  One matrix per lane: the steady-state kernels (70_n1.inc, 71_steady_march.inc); also compiled for the host.
+template <int NV>
+__device__ __forceinline__ real rmt_invert_n(real (&a)[NV][NV]) {
+    real pmin = real(__builtin_inf());
+#pragma unroll
+    for (int p = 0; p < NV; ++p) {
+        pmin = rmt_min(pmin, rmt_abs(a[p][p]));
+        const real ip = rmt_rcp(a[p][p]);
+        a[p][p] = real(1);
+#pragma unroll
+        for (int c = 0; c < NV; ++c) a[p][c] *= ip;
+#pragma unroll
+        for (int r = 0; r < NV; ++r) {
+            if (r != p) {
+                const real f = a[r][p];
+                a[r][p] = real(0);
+#pragma unroll
+                for (int c = 0; c < NV; ++c) a[r][c] -= f * a[p][c];
+            }
+        }
+    }
+    return pmin;
+}
 

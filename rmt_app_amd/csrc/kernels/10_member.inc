@@ -26,7 +26,7 @@ RMT_KINETICS_SOURCE
 #ifndef RMT_KIN_USES_C
 #define RMT_KIN_USES_C 1
 #endif
-#define RMT_NODE_X_CC (RMT_NODE_X_FROM_STATE && !RMT_KIN_USES_C && !RMT_WITH_ROS4)
+#define RMT_NODE_X_CC (RMT_NODE_X_FROM_STATE && !RMT_KIN_USES_C && !RMT_WITH_ROS4 && !RMT_WITH_MARCH)
 // Four more (profiles/node_cuts.md, DESIGN.md section 3j), each its own switch, default on:
 //  RMT_NODE_NO_X          no mole fractions at all where the rates depend on (x, P) only through the partial pressures
 //                         x_i P (RMT_KIN_XP_INVARIANT, from the lowering) and under the conditions of RMT_NODE_X_CC:

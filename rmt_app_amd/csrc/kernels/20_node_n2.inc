@@ -216,7 +216,7 @@ __device__ __forceinline__ preal rmt_pressure_next(const RmtMember& m, const pre
     return a * P + m.beta;                                // :3979
 }
 
-#if RMT_WITH_ROS4
+#if RMT_WITH_ROS4 || RMT_WITH_MARCH
 #ifndef RMT_ROS_JAC_FD
 #define RMT_ROS_JAC_FD 0         // 1: node Jacobian by V forward differences of the node function (the round-1 form)
 #endif
@@ -314,5 +314,5 @@ __device__ __forceinline__ void rmt_node_jac(const RmtMember& m, const RmtNode& 
     }
 #endif
 }
-#endif   // RMT_WITH_ROS4
+#endif   // RMT_WITH_ROS4 || RMT_WITH_MARCH
 

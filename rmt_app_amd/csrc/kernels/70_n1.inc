@@ -4,30 +4,7 @@
 #endif
 // ===================================================================== kernel: steady-state model N1 (batched)
 // (node functions rmt_n1_init / rmt_n1_rhs / rmt_n1_rhs_jac of the steady model RMT_SS_MODEL and its member-row layout:
-// see the node-physics section above)
-template <int NV>
-__device__ __forceinline__ real rmt_invert_n(real (&a)[NV][NV]) {
-    real pmin = real(__builtin_inf());
-#pragma unroll
-    for (int p = 0; p < NV; ++p) {
-        pmin = rmt_min(pmin, rmt_abs(a[p][p]));
-        const real ip = rmt_rcp(a[p][p]);
-        a[p][p] = real(1);
-#pragma unroll
-        for (int c = 0; c < NV; ++c) a[p][c] *= ip;
-#pragma unroll
-        for (int r = 0; r < NV; ++r) {
-            if (r != p) {
-                const real f = a[r][p];
-                a[r][p] = real(0);
-#pragma unroll
-                for (int c = 0; c < NV; ++c) a[r][c] -= f * a[p][c];
-            }
-        }
-    }
-    return pmin;
-}
-
+// see the node-physics section above; the V1 x V1 inverse rmt_invert_n: 00_config_math.inc)
 #ifndef RMT_N1_SCHEME
 #define RMT_N1_SCHEME 1          // 1: RODAS4, 0: Kaps-Rentrop/Shampine
 #endif

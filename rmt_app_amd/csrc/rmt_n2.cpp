@@ -59,7 +59,8 @@ struct rmt_n2_handle {
     hipModule_t module = nullptr;
     hipFunction_t f_rhs = nullptr, f_rk4_reg = nullptr, f_rk4_mem = nullptr, f_rk45_reg = nullptr,
                   f_rk45_mem = nullptr, f_multistep = nullptr, f_rk4_chain = nullptr, f_ros4 = nullptr, f_n1 = nullptr,
-                  f_ros4_chain = nullptr, f_rk45_chain = nullptr, f_rk4_redo = nullptr, f_rk4_chain_redo = nullptr;
+                  f_ros4_chain = nullptr, f_rk45_chain = nullptr, f_rk4_redo = nullptr, f_rk4_chain_redo = nullptr,
+                  f_march = nullptr;
     unsigned long long* d_rings = nullptr;   // tagged-word links of the chained stiff stepper: rings, decision slots, abort words
     size_t ring_bytes = 0;
     double* d_members1 = nullptr;
@@ -246,6 +247,7 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
         {"rmt_n2_ros4_mem", &rmt_n2_handle::f_ros4, false},
         {"rmt_n1_ros4", &rmt_n2_handle::f_n1, false},
         {"rmt_n2_ros4_chain", &rmt_n2_handle::f_ros4_chain, false},
+        {"rmt_n2_steady_march", &rmt_n2_handle::f_march, false},
     };
     for (const auto& k : kernels) {
         const hipError_t e = hipModuleGetFunction(&(h->*k.f), h->module, k.name);
@@ -697,6 +699,24 @@ extern "C" int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* ou
                     (void*)&h0, (void*)&ms, (void*)&stats, (void*)&h->d_flags};
     HIP_OK(hipEventRecord(h->ev0, h->stream));
     HIP_OK(hipModuleLaunchKernel(h->f_n1, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    HIP_OK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return 0;
+}
+
+extern "C" int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, int64_t max_iter, rmt_n2_stats* stats) {
+    if (!h || !y_out || !stats) return fail("null argument");
+    if (!(tol > 0) || max_iter < 1) return fail("bad steady-march arguments (tolerance > 0, max_iter >= 1)");
+    if (!h->f_march) return fail("code object has no rmt_n2_steady_march (generate it with RMT_WITH_MARCH)");
+    if (h->fp32) return fail("the steady-state march is fp64 only");
+    ON_DEVICE(h);
+    int N = h->N, E = h->E;
+    long long mi = (long long)max_iter;
+    void* args[] = {(void*)&y_out, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
+                    (void*)&h->d_flags};
+    // one reactor per lane, one wave per workgroup (the shape of rmt_n1_ros4)
+    HIP_OK(hipEventRecord(h->ev0, h->stream));
+    HIP_OK(hipModuleLaunchKernel(h->f_march, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
     HIP_OK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     return 0;

@@ -14,14 +14,15 @@ import os
 
 import numpy as np
 
-from . import control, hipbind, launches, monitor, plan, schedule
+from . import control, hipbind, initial, launches, monitor, plan, schedule
 from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
 
 FLAG_PRESSURE = 32
 DEVICE_IVPS = ("hip-rk4", "hip-rk45", "hip-ros4", "hip-auto", "AM", "hip-ab3")
-FEATURE_DEFINES = {"ros4": "RMT_WITH_ROS4", "n1": "RMT_WITH_N1"}
+FEATURE_DEFINES = {"ros4": "RMT_WITH_ROS4", "n1": "RMT_WITH_N1", "march": "RMT_WITH_MARCH"}
+MARCH_BLOCK = 64         # csrc/kernels/71_steady_march.inc: one reactor per lane, one wave per workgroup
 
 
 N_CUS = 256          # MI355X; the C library clamps the team count to the device's real CU count
@@ -298,6 +299,29 @@ def code_plan(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None,
     return CodePlan(block, npt, lds_state, defs, tuple(features))
 
 
+def march_plan(mech, N, defines=None, rows=None):
+    """The code object of the steady-state march (solver-config "initial", csrc/kernels/71_steady_march.inc): a unit of
+    its own - the stepper's code object and its cache key are those of a run without the key.  block = 64 (one reactor per
+    lane), the family "march" (RMT_WITH_MARCH: the analytic node Jacobian without the stiff stepper's kernels), no
+    rate-constant cache, fp64.  Of the run's ``defines`` only the row layout travels (RMT_FORCING: the rows are the
+    stepper's); the member fields stay run-time values, so one object serves every operating point of a mechanism."""
+    defs = {"RMT_KCACHE": "0", "RMT_KCACHE_CHAIN": "0"}
+    if is_forced(defines):
+        defs["RMT_FORCING"] = forcing_level(defines)
+    return code_plan(mech, N, False, None, MARCH_BLOCK, 1, None, defs, ("march",), rows, specialize=False)
+
+
+def code_plans(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),
+               rows=None, specialize=None, literals=None, newton=True):
+    """EVERY code object a run loads, as CodePlans: the stepper's (code_plan with the same arguments, the feature "march"
+    taken out) and, with the feature "march", the unit of the steady-state march behind it (march_plan)."""
+    step = tuple(f for f in features if f != "march")
+    plans = [code_plan(mech, N, fp32, E, block, npt, lds_state, defines, step, rows, specialize, literals, newton)]
+    if "march" in features:
+        plans.append(march_plan(mech, N, defines, rows))
+    return plans
+
+
 def plan_unit(mech, fp32, cp):
     """(translation unit, cache key) of a CodePlan"""
     tpl = hipbind.kernel_template()
@@ -444,6 +468,7 @@ class N2Device:
         self.jacobian_evals = (mech.V + (1 if getattr(mech, "model", "N2") == "M2" else 0)) if fd else 1
         self.dtype = torch.float32 if self.fp32 else torch.float64
         self._stats = torch.zeros((self.E, 4), dtype=torch.float64, device=self.device)
+        self.march = None       # a second device of the same rows with the steady-state march (attach_march)
         self.use_current_stream()
 
     # -- plumbing
@@ -490,6 +515,9 @@ class N2Device:
         if getattr(self, "_mon", None) is not None:
             self._mon.close()
             self._mon = None
+        if getattr(self, "march", None) is not None:
+            self.march.close()
+            self.march = None
         if getattr(self, "h", None):
             hipbind.lib().rmt_n2_destroy(self.h)
             self.h = None
@@ -574,6 +602,42 @@ class N2Device:
         hipbind.check(hipbind.lib().rmt_n2_ros4(self.h, C.c_void_p(y.data_ptr()), float(t0), float(t1),
                                                 float(rtol), float(atol), float(h0), int(max_steps),
                                                 C.c_void_p(self._stats.data_ptr())))
+
+    def attach_march(self):
+        """A second handle on the same member rows whose code object holds the steady-state march (march_plan): the
+        stepper's own code object stays what it is without it.  steady_march / march_result then go through it."""
+        if "march" not in self.features and self.march is None:
+            if self.fp32 or getattr(self.mech, "model", "N2") != "N2":
+                raise hipbind.RmtN2Error("the steady-state march is for model N2 in fp64")
+            cp = march_plan(self.mech, self.N, self.defines, self.members)
+            self.march = N2Device(self.mech, self.members, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
+                                  defines=cp.defines, specialize=False, features=cp.features)
+        return self
+
+    def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
+        """In place: every member's state becomes the discrete steady state f(y) = 0 of its device rows (a forced row: its
+        values at the row's reference time), found by marching from the inlet with one V x V solve per node
+        (rmt_n2_steady_march).  Queued on the stream, nothing is synchronised; march_result reads what came of it.
+        Needs features=("march",), or attach_march()."""
+        self._chk_state(y)
+        if "march" not in self.features:
+            if self.march is None:
+                raise hipbind.RmtN2Error("create the device with features=('march',) or call attach_march() to use the "
+                                         "steady-state march")
+            return self.march.steady_march(y, tol, max_iter)
+        hipbind.check(hipbind.lib().rmt_n2_steady_march(self.h, C.c_void_p(y.data_ptr()), float(tol), int(max_iter),
+                                                        C.c_void_p(self._stats.data_ptr())))
+
+    def march_result(self):
+        """(stats, flags) of the last steady_march (synchronises): per member the worst node's scaled residual, the node
+        that failed (-1: none), the largest per-node step count and the number of nodes that needed a rejected step; the
+        status words, read and cleared."""
+        if "march" not in self.features and self.march is not None:
+            return self.march.march_result()
+        raw = self._stats.cpu().numpy()
+        its, damped = step_counts(raw)
+        return ({"scaled-residual": raw[:, 0].copy(), "failed-node": raw[:, 1].astype(np.int64), "iterations": its,
+                 "nodes-damped": damped}, self.status())
 
     def n1_profile(self, rows1, nout, rtol, atol, h0, max_steps, V1=None):
         """Steady-state model N1 (needs features=("n1",)): one profile per member row of ``rows1`` (layout M1_*),
@@ -679,6 +743,17 @@ class AutoStepper:
 
     def rk45_stats(self):
         return self.last.rk45_stats()
+
+    def attach_march(self):
+        self.d45.attach_march()
+        return self
+
+    def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
+        """the steady-state march on the rows of the explicit device (both devices hold the same rows)"""
+        self.d45.steady_march(y, tol, max_iter)
+
+    def march_result(self):
+        return self.d45.march_result()
 
     def monitor(self, y, out, residual=False):
         self.last.monitor(y, out, residual)
@@ -876,7 +951,7 @@ def mechanism_for(modelInput, inputs, cfg):
 
 
 def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=None, npt=None, defines=None,
-                 features=(), forcing=None):
+                 features=(), forcing=None, march=False):
     """Device + initial state for the members THIS process integrates.
 
     Single process: all of ``inputs``.  As one rank of a torch.distributed job (``sync``, see
@@ -884,7 +959,11 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     code object, sweep-invariant member fields agreed over all ranks become kernel literals.
     Returns (device, named constants of the local members, local initial states [E_local][V*N]).
     ``forcing`` (a Forcing, solver-config "schedule"): the code object is generated with RMT_FORCING (2 when the schedule
-    moves the feed composition, else 1), the rows get their tail, and the host fixes the kernel form (forced_mode)."""
+    moves the feed composition, else 1), the rows get their tail, and the host fixes the kernel form (forced_mode).
+    ``march`` (solver-config "initial", single process): a second handle on the same rows holds the steady-state march
+    (N2Device.attach_march)."""
+    if march and sync is not None:
+        raise NotImplementedError("solver-config 'initial' is not available in a multi-rank run")
     if forcing is not None:
         defines = {**(defines or {}), "RMT_FORCING": forcing.sched.forcing_level}
     if sync is None:
@@ -896,6 +975,12 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
         dev = device_cls()(mech, rows, zNo, fp32=fp32, block=block, npt=npt, defines=defines, features=features)
         if forcing is not None:
             forcing.fix_mode(dev, "hip-ros4" if "ros4" in features else "explicit")
+        if march:
+            try:
+                dev.attach_march()
+            except Exception:
+                dev.close()
+                raise
         return dev, [nm for nm, _ in pairs], IV
     # Multi-rank: every rank-LOCAL phase (packing, the rank-0 compile inside DistributedEnsemble, loading the
     # module and allocating on the device) runs under ensemble.guarded / agree: a failure on one rank is raised
@@ -921,7 +1006,7 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     return dev, ens.named, ens.IV
 
 
-def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None, forcing=None):
+def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None, forcing=None, march=False):
     """The two devices of ivp "hip-auto" (explicit pair in its on-chip geometry, Rosenbrock family) behind one
     AutoStepper; an explicit `block` / `nodes-per-thread` of the solver-config applies to the explicit device."""
     if block is None and forcing is not None:       # (no chained chunks: they do not carry the forcing)
@@ -931,7 +1016,7 @@ def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, np
     else:
         b45, n45, d45 = block, npt, {}
     dev45, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=b45, npt=n45,
-                                          defines={**(defines or {}), **d45}, forcing=forcing)
+                                          defines={**(defines or {}), **d45}, forcing=forcing, march=march)
     def make_ros4():
         return open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=ros4_block(mech.V, zNo, fp32),
                             npt=1, defines=defines, features=("ros4",), forcing=forcing)[0]
@@ -1230,6 +1315,28 @@ def steady_profiles(modelInput, members_inputs, pack, nout, defines=None, extra=
     return mech, [nm for nm, _ in pairs], U, stats
 
 
+def start_steady(dev, y, ini, mech):
+    """solver-config "initial": "steady" - the state y becomes every member's steady state (N2Device.steady_march on the
+    device rows as they are), then rmt_n2_rhs and ONE monitor reduction measure max_n |dy/dt| of what the run starts from.
+    Raises through flag_error when a member's march failed - the message names the member and the node; there is no
+    fallback to the cold start.  Returns the members' result entries."""
+    dev.steady_march(y, ini.tolerance, ini.max_iterations)
+    st, flags = dev.march_result()
+    err = flag_error(flags)
+    if err is not None:
+        e = int(np.nonzero(flags)[0][0])
+        raise type(err)("solver-config 'initial': the steady-state march failed at node %d of member %d (%d pseudo-time "
+                        "steps, 'max-iterations' = %d): %s"
+                        % (int(st["failed-node"][e]), e, int(st["iterations"][e]), ini.max_iterations, err))
+    E = y.shape[0]
+    import torch
+    out = torch.zeros((E, mech.V, monitor.SLOTS), dtype=torch.float64, device=y.device)
+    dev.monitor(y, out, residual=True)
+    res = out.cpu().numpy()[:, :, monitor.RESIDUAL].max(axis=1)
+    dev.raise_on_flags()
+    return [ini.result_entry(res[e], st["iterations"][e], st["nodes-damped"][e]) for e in range(E)]
+
+
 def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result, fp32=False, defines=None,
                 with_schedule=False, outlet=False, display=False):
     """What run_n2 and m2.run_m2 share: the ranks of a torchrun job, the geometry of the `ivp`, the device(s), the walk
@@ -1264,6 +1371,8 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
     mon = monitor.parse(modelInput, tNo)
     if mon is not None:
         mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
+    # "initial": where the run starts (initial.py); absent = None = the reference's cold start, exactly the run without it
+    ini = initial.parse(modelInput, sync is not None) if with_schedule else None
     # the ONE launch list of the run; a sample that fell on a mark carries that mark's time from here on (result entries)
     walk, sample_times, control_times = launches.merge(
         opT, tNo, forced_by.times if forced_by is not None else (), mon.times if mon is not None else None,
@@ -1290,11 +1399,12 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, **({"chain": False} if forcing is not None else {"E": E_gpu}))
         defines.update(geo_defs)
     if ivp == "hip-auto":
-        dev, named_local, IV = open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block, npt, forcing=forcing)
+        dev, named_local, IV = open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block, npt, forcing=forcing,
+                                         march=ini is not None)
     else:
         dev, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=block, npt=npt,
                                             defines=defines, features=("ros4",) if ivp == "hip-ros4" else (),
-                                            forcing=forcing)
+                                            forcing=forcing, march=ini is not None)
     # the process that returns the results (rank 0, or the only one) packs EVERY member
     packer = sync is None or sync.rank == 0
     try:
@@ -1303,6 +1413,8 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         else:
             named = guarded(sync, lambda: [pack(mi, mech, zNo)[0] for mi in inputs] if packer else [])
         y = guarded(sync, dev.to_device, IV)
+        # (the device rows are those of t = 0: a forced run's were attached for its first launch, which starts there)
+        started = start_steady(dev, y, ini, mech) if ini is not None else None
         packs = [[] for _ in named]
 
         def on_interval(i, t1, Yh):
@@ -1337,6 +1449,11 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         if members_inputs:
             for entry, c in zip(res["ensemble"], entries):
                 entry["control"] = c
+    if started is not None:
+        res["initial"] = started[0]
+        if members_inputs:
+            for entry, st in zip(res["ensemble"], started):
+                entry["initial"] = st
     if monitors:
         res["monitor"] = monitors[0]
         if members_inputs:

@@ -308,7 +308,8 @@ class Mechanism:
         # Not in fp32 either: v_rcp_f32 has no Newton step that would turn the reciprocal of an overflowed product into
         # NaN, it returns 0 and the rates would be finite and wrong - and the range is 1e+-38 there.  The same goes for
         # the plain 1.0/b of a kernel built with RMT_FAST_MATH 0.
-        with_jac = bool((defines or {}).get("RMT_WITH_ROS4") or (defines or {}).get("RMT_WITH_N1"))
+        with_jac = bool((defines or {}).get("RMT_WITH_ROS4") or (defines or {}).get("RMT_WITH_N1")
+                        or (defines or {}).get("RMT_WITH_MARCH"))
         batch = str((defines or {}).get("RMT_DIV_BATCH", "1")) != "0" and not with_jac and not fp32 \
             and str((defines or {}).get("RMT_FAST_MATH", "1")) != "0"
         kin = self.device_dag().emit("rmt_kinetics", const_table=bool((defines or {}).get("RMT_KINETICS_KTAB")),
@@ -318,8 +319,9 @@ class Mechanism:
                                      kcache_thr=(defines or {}).get("RMT_KCACHE_THR"),
                                      div_batch=batch)
         kin += self.node_kinetics(defines, fp32, with_jac)
-        if (defines or {}).get("RMT_WITH_ROS4"):
-            # the stiff stepper's node Jacobian is analytic: rates AND their partials by T, x_i, C_i
+        if (defines or {}).get("RMT_WITH_ROS4") or (defines or {}).get("RMT_WITH_MARCH"):
+            # the node Jacobian of the stiff stepper and of the steady-state march is analytic: rates AND their partials
+            # by T, x_i, C_i
             kin += self.device_dag().gradient().emit_jac("rmt_kinetics_jac")
         if (defines or {}).get("RMT_WITH_N1"):
             # steady-state model N1: the pressure is a state variable, so the partials by P as well

@@ -34,6 +34,8 @@ def rmtExe(modelInput):
         check_model(modelInput)               # solver-config 'monitor': models N2 and M2 only
         from .control import check_model as check_control
         check_control(modelInput)             # solver-config 'control': model N2 only
+        from .initial import check_model as check_initial
+        check_initial(modelInput)             # solver-config 'initial': model N2 only
         if modelType == "N2":
             from .n2 import run_n2
             ensemble = modelInput['solver-config'].get('ensemble')

@@ -5,10 +5,11 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
 coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
-closed-loop runs with the sampled PI controller, G15).
+closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|syn12]: discrete steady states of model N2,
+G17 - like G13..G15 it runs SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
 """
@@ -1212,6 +1213,65 @@ def g_control(which=None):
         print("G15 %s written (%.0f s)" % (name, time.time() - t0))
 
 
+# ------------------------------------------------------------------ G17: discrete steady states of model N2
+# (solver-config "initial": "steady", rmt_app_amd/initial.py).  SciPy on the oracle's vectorised RHS: the transient from
+# the reference's cold start until max|f| stops falling, then a polish of f(y) = 0 on the full system.  Nothing of the
+# product is imported.  The isothermal ch4 case relaxes far more slowly (2.5e-2 after 10 s) and is not a golden.
+G17_CASES = {"dme_script": {"input": "dme_script", "zNo": 20}, "dme_nb": {"input": "dme_nb", "zNo": 20},
+             "syn12": {"input": "syn12", "zNo": 20}}
+G17_GATE = 1e-9          # a case whose final max|f| under the oracle RHS exceeds this is not written
+G17_CHUNK = 10.0         # simulated seconds per LSODA leg
+G17_T_MAX = 400.0
+
+
+def g17_state(case, rtol=1e-10, atol=1e-13):
+    """(state [V*N], max|f| reached, simulated time used, residual after LSODA alone)"""
+    import scipy.optimize
+    from oracle import n2_oracle as O
+    pr = O.setup_n2(INP.ALL_N2_INPUTS[case["input"]](), zNo=case["zNo"])
+    f = O.make_rhs_vec(pr)
+    y, t, prev = np.array(pr["IV"], dtype=float), 0.0, np.inf
+    while t < G17_T_MAX:
+        t0 = time.time()
+        sol = REAL_SOLVE_IVP(f, (t, t + G17_CHUNK), y, method="LSODA", rtol=rtol, atol=atol)
+        if not sol.success:
+            raise RuntimeError(sol.message)
+        y, t = sol.y[:, -1], t + G17_CHUNK
+        r = float(np.max(np.abs(f(t, y))))
+        print("G17 %s: t = %.0f s max|f| = %.3e nfev=%d %.0f s" % (case["input"], t, r, sol.nfev, time.time() - t0), flush=True)
+        if not r < 0.5*prev:            # stopped falling
+            break
+        prev = r
+    r_ode = float(np.max(np.abs(f(t, y))))
+    best, r_best = y, r_ode
+    sol = scipy.optimize.root(lambda v: f(0.0, v), y)        # (the default method, MINPACK's hybrd, with its default tolerance)
+    r = float(np.max(np.abs(f(0.0, sol.x))))
+    print("G17 %s: root max|f| = %.3e" % (case["input"], r), flush=True)
+    if np.all(np.isfinite(sol.x)) and r < r_best:          # (a polish that does not lower max|f| leaves the transient's state)
+        best, r_best = np.array(sol.x, dtype=float), r
+    return best, r_best, t, r_ode
+
+
+def g_steady_state(which=None):
+    path = os.path.join(GOLD, "g17_steady.json")
+    meta = {"cases": {}, "gate": G17_GATE, "rtol": 1e-10, "atol": 1e-13,
+            "reference": "SciPy LSODA on oracle.n2_oracle.make_rhs_vec from the oracle's IV until max|f| stops falling, "
+                         "then scipy.optimize.root on the full system"}
+    if which and os.path.exists(path):
+        with open(path) as fh:
+            meta["cases"] = json.load(fh)["cases"]
+    for name in ([which] if which else list(G17_CASES)):
+        case = G17_CASES[name]
+        y, r, t, r_ode = g17_state(case)
+        if not r <= G17_GATE:
+            raise SystemExit("G17 %s: max|f| = %.3e under the oracle RHS exceeds the gate %.1e - not written" % (name, r, G17_GATE))
+        np.savez_compressed(os.path.join(GOLD, "g17_steady_%s.npz" % name), state=y, residual=r)
+        meta["cases"][name] = dict(case, residual=r, time=t, residual_lsoda=r_ode)
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+        print("G17 %s written: max|f| = %.3e after %.0f s (LSODA alone %.3e)" % (name, r, t, r_ode), flush=True)
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1245,6 +1305,8 @@ def main(argv):
             g_feed(what.split("=", 1)[1] if "=" in what else None)
         elif what == "control" or what.startswith("control="):
             g_control(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "steady" or what.startswith("steady="):
+            g_steady_state(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

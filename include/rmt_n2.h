@@ -117,7 +117,9 @@ typedef struct rmt_n2_plan {
     int32_t ros4_nodes_per_block; /* mesh nodes one workgroup of the stiff stepper covers: 0 = `block` (one node per lane);
                               * block / 4 for code objects generated with RMT_ROS_QUAD (one node on four lanes, the
                               * layout for mechanisms wider than 8 variables, kernels/61_ros4_quad.inc) */
-    int32_t reserved;
+    int32_t profiled;        /* 1: the code object was generated with RMT_PROFILE (solver-config "axial-profile": catalyst
+                              * activity and coolant offset per mesh node, kernels/12_profile.inc) and every launch needs
+                              * the table of rmt_n2_set_profile; 0: none (the field was `reserved`, always 0) */
     const void* code_object; /* gfx950 code object from rmt_n2_compile (host memory) */
     size_t code_size;
     const double* members;   /* host [E][16+S+NU] packed constants */
@@ -160,6 +162,16 @@ int rmt_n2_set_members(rmt_n2_handle* h, const double* members);
  * fields P0, THETA_IN and TM hold the values at the start of the launch and the tail {t_ref, d THETA_IN/dt, d P0/dt,
  * d TM/dt} the time of that start and the slopes over the launch (kernels/11_forcing.inc). */
 int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members_pinned);
+
+/* Axial profiles (handles created with plan.profiled = 1 only; on any other handle this is an error): `table_host` is
+ * [E][2][N] doubles, per member first the N catalyst activities a_n >= 0, then the N coolant offsets delta_n [K], for the
+ * mesh nodes z_n = n/(N-1).  The node function of such a code object multiplies every reaction rate of node n by a_n and
+ * uses the coolant temperature Tm = tm + delta_n in its wall term, where tm is the member field M_TM as it is at that
+ * stage (a forced coolant moves the common level, the zones keep their offsets; tm == 0 stays the adiabatic switch).
+ * ONE synchronous upload into a buffer the handle owns (freed by rmt_n2_destroy), to be made before the first launch; it
+ * is not on the launch path.  Until it has been made every launch entry point of a profiled handle returns an error
+ * instead of launching.  A profiled code object has no chained kernels and no multistep kernel. */
+int rmt_n2_set_profile(rmt_n2_handle* h, const double* table_host);
 
 int rmt_n2_rhs(rmt_n2_handle* h, double t, const void* y, void* dydt);
 int rmt_n2_rk4(rmt_n2_handle* h, void* y_inout, double t0, double dt, int64_t nsteps);

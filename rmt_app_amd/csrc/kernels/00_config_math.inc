@@ -80,6 +80,11 @@
 #ifndef RMT_FORCING
 #define RMT_FORCING 0
 #endif
+// RMT_PROFILE 1 (solver-config "axial-profile", 12_profile.inc): catalyst activity and coolant offset per mesh node, read
+// from a table beside the member rows; the rows themselves keep their layout
+#ifndef RMT_PROFILE
+#define RMT_PROFILE 0
+#endif
 #if RMT_FORCING == 2
 #define RMT_NM (16 + RMT_S + RMT_NU + 4 + RMT_S)
 #elif RMT_FORCING

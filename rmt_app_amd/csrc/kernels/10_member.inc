@@ -59,6 +59,13 @@ struct RmtMember {
     preal p0, alpha_k, beta;
     real cin[RMT_S];
     real user[RMT_NU > 0 ? RMT_NU : 1];
+#if RMT_PROFILE
+    // axial profile (12_profile.inc): the member's table [2][prof_n] = {activity a_n, coolant offset delta_n}, bound by the
+    // kernel (rmt_profile_bind), and the two values of the node a per-lane march is solving (identity unless it sets them)
+    const double* prof;
+    int prof_n;
+    real act, dtm;
+#endif
 };
 
 // A member field whose value is identical for every reactor of the launch can be baked into the
@@ -169,6 +176,12 @@ __device__ __forceinline__ void rmt_load_member(const double* __restrict__ row, 
     for (int k = 0; k < RMT_NU; ++k) m.user[k] = real(row[M_USER + k]);
 #if RMT_NU == 0
     m.user[0] = real(0);
+#endif
+#if RMT_PROFILE
+    m.prof = nullptr;
+    m.prof_n = 0;
+    m.act = real(1);
+    m.dtm = real(0);
 #endif
 }
 

@@ -12,6 +12,9 @@ struct RmtNode {
 #if RMT_NODE_CS
     real ict;      // 1/sum cs; x holds cs, MoT is 1e3 M/T and M is not formed
 #endif
+#if RMT_PROFILE
+    real act, dtm; // catalyst activity and coolant offset of this node (12_profile.inc); rmt_node_pre: the identity (1, 0)
+#endif
 };
 
 // rmt_node_pre in two halves around its reciprocal, so that rmt_rhs_block can take the reciprocals of a lane's two nodes
@@ -19,6 +22,10 @@ struct RmtNode {
 __device__ __forceinline__ real rmt_node_pre_sum(const RmtMember& m, const real* __restrict__ ys, RmtNode& nd,
                                                  real& ctot) {
     ctot = real(0);
+#if RMT_PROFILE
+    nd.act = real(1);                                     // a caller that knows its node overwrites the two
+    nd.dtm = real(0);
+#endif
 #if RMT_NODE_X_CC
 #pragma unroll
     for (int i = 0; i < RMT_S; ++i) {                     // ctot, inv_ctot below: of the clamped state (no cmax)
@@ -154,7 +161,11 @@ __device__ __forceinline__ void rmt_node_post(const RmtMember& m, const RmtNode&
 #pragma unroll
         for (int q = 0; q < RMT_R; ++q) hq[q] = dcp[q] * (T - RMT_TREF) + RMT_DH25[q];   // :4025-4028
     }
+#if RMT_PROFILE
+    const real qm = (m.tm == real(0)) ? real(0) : (FMR ? m.qm_kf : m.ua) * ((m.tm + nd.dtm) - T);   // coolant of this zone
+#else
     const real qm = (m.tm == real(0)) ? real(0) : (FMR ? m.qm_kf : m.ua) * (m.tm - T);    // rmtUtility.py:438-445
+#endif
     // const_T2/GaHeCoTe0 (:4077, 4118) = F1/(GaHeCoTe0 rho* Cp*), rho* = P M/(R T GaDe0) (:3964-3966),
     // Cp* = Cp/Cp0 (:4016): the four per-reactor constants arrive as ONE (member field GAIN_K; m.gain_k / gain_kf: with the
     // factors of the cuts, rmt_load_member).  RMT_NODE_CS: P is P / sum cs, MoT is 1e3 M/T and cpm is sum cs_i cpbar_i -
@@ -189,6 +200,12 @@ __device__ __forceinline__ void rmt_node_post(const RmtMember& m, const RmtNode&
             rmt_nocache_t nc;
             rmt_kinetics(nd.T, nd.invT, P, nd.x, nd.C, m.user, r, flag, nc);    // :3989-3992
         }
+#if RMT_PROFILE
+        // catalyst activity: every rate of this node, whichever rate function returned it (with FMR they carry FM as well).
+        // Rates handed in (HAVE_R) come from rmt_node_jac, which has scaled them already
+#pragma unroll
+        for (int q = 0; q < RMT_R; ++q) r[q] *= nd.act;
+#endif
     }
     real src[RMT_S];
     rmt_species_source(r, src);                                         // :4000 (sparse nu^T r)
@@ -233,6 +250,10 @@ __device__ __forceinline__ void rmt_node_jac(const RmtMember& m, const RmtNode& 
     const real P = real(Pz);
     real r[RMT_R], drdT[RMT_R], drdx[RMT_R][RMT_S], drdC[RMT_R][RMT_S];
     rmt_kinetics_jac(nd.T, nd.invT, P, nd.x, nd.C, m.user, r, drdT, drdx, drdC, flag);
+#if RMT_PROFILE
+#pragma unroll
+    for (int q = 0; q < RMT_R; ++q) r[q] *= nd.act;       // catalyst activity: the scaled rates leave in rout, G below
+#endif
 #pragma unroll
     for (int q = 0; q < RMT_R; ++q) rout[q] = r[q];
     real ctot = real(0);
@@ -253,6 +274,10 @@ __device__ __forceinline__ void rmt_node_jac(const RmtMember& m, const RmtNode& 
         for (int j = 0; j < RMT_S; ++j) G[q][j] = act[j] * (drdC[q][j] * ctot + (drdx[q][j] - sx));
 #if !RMT_ISO
         G[q][RMT_S] = m.tf * drdT[q];
+#endif
+#if RMT_PROFILE
+#pragma unroll
+        for (int c = 0; c < RMT_V; ++c) G[q][c] *= nd.act;
 #endif
     }
     // species rows: k_i = -F1 (c_i - up_i) inv_dz + FM sum_q nu_qi r_q
@@ -293,7 +318,11 @@ __device__ __forceinline__ void rmt_node_jac(const RmtMember& m, const RmtNode& 
         dqrT += G[q][RMT_S] * hq[q] + r[q] * (m.tf * (dcp[q] + (T - RMT_TREF) * ddcp[q]));
     }
     const bool wall = !(m.tm == real(0));
+#if RMT_PROFILE
+    const real qm = wall ? m.ua * ((m.tm + nd.dtm) - T) : real(0);
+#else
     const real qm = wall ? m.ua * (m.tm - T) : real(0);
+#endif
     const real dqmT = wall ? -(m.ua * m.tf) : real(0);
     const real icpm = rmt_rcp(cpm);
     const real gain = m.inv_hecote * rmt_rcp(P * nd.MoT) * icpm;

@@ -267,6 +267,9 @@ struct RmtLocal {       // what a node's balances see of the rest of the reactor
 struct RmtCarry {       // workgroup-uniform hand-over between consecutive node blocks
     preal P;            // pressure at the first node of the block
     real up[RMT_V];     // clamped state of the node just upstream of the block (inlet for block 0)
+#if RMT_PROFILE
+    int node0;          // global index of the block's first node (12_profile.inc; callers that walk node blocks set it)
+#endif
 };
 
 __device__ __forceinline__ void rmt_carry_inlet(const RmtMember& m, RmtCarry& c) {
@@ -276,5 +279,6 @@ __device__ __forceinline__ void rmt_carry_inlet(const RmtMember& m, RmtCarry& c)
 #if !RMT_ISO
     c.up[RMT_S] = m.theta_in;                                           // :4108
 #endif
+    RMT_PROFILE_AT(c, 0)
 }
 

@@ -43,6 +43,10 @@ __device__ __forceinline__ void rmt_rhs_block(const RmtMember& m, RmtShared& sh,
         preal a;
         if constexpr (PAIR) a = rmt_node_pre_fin(m, nd[j], pair_ct[j], pair_inv[j]);
         else a = rmt_node_pre(m, ys[j], nd[j]);
+#if RMT_PROFILE
+        static_assert(CHAIN == 0, "RMT_PROFILE: the chained forms do not carry the profile");
+        RMT_PROFILE_NODE(m, nd[j], carry.node0 + (int)threadIdx.x * NPT + j)     // issued ahead of the scan and the barrier
+#endif
         loc[j].a = (j < nvalid) ? a : preal(1);
         loc[j].b = (j < nvalid) ? m.beta : preal(0);
         mine = rmt_then(mine, loc[j]);

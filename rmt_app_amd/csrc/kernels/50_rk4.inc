@@ -23,6 +23,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_RHS_WAVES) void rmt_n2_rh
 #else
         RmtMember m;
         rmt_load_member(members + (size_t)e * RMT_NM, m);
+        RMT_PROFILE_BIND(m, e, N)
 #endif
         RmtCarry carry;
         rmt_carry_inlet(m, carry);
@@ -40,6 +41,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_RHS_WAVES) void rmt_n2_rh
 #pragma unroll
                 for (int i = 0; i < RMT_V; ++i) ys[0][i] = ye[(size_t)i * N + node];
             }
+            RMT_PROFILE_AT(carry, base)
             rmt_rhs_block<1, true>(m, sh, ph, ys, valid ? 1 : 0, carry, k, flag);
             if (valid) {
 #pragma unroll
@@ -151,6 +153,7 @@ __device__ __forceinline__ void rmt_rk4_reg_body(
 #else
     RmtMember m;
     rmt_load_member(members + (size_t)e * RMT_NM, m);
+    RMT_PROFILE_BIND(m, e, N)                 // (the reactor is one block: carry.node0 stays 0)
 #endif
     RmtCarry carry;
     rmt_carry_inlet(m, carry);
@@ -417,6 +420,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk4_reg_redo(
 #define RMT_RK4C_KC 0
 #endif
 
+#if !RMT_PROFILE      // (a profiled run keeps a reactor on one workgroup: the chained form does not carry the profile)
 template <bool CACHED, bool REDO>
 __device__ __forceinline__ void rmt_rk4_chain_body(
         real* __restrict__ y, const double* __restrict__ members, const int N, const int E,
@@ -681,6 +685,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk4_chain_redo(
                                     backup, redo, falt);
 }
 #endif
+#endif   // !RMT_PROFILE
 
 // ===================================================================== kernel: RK4, state in memory
 // Same integrator for any N with ONE workgroup per reactor.  Information only travels downstream and
@@ -718,6 +723,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk4_mem(
     const int e = blockIdx.x;
     RmtMember m;
     rmt_load_member(members + (size_t)e * RMT_NM, m);
+    RMT_PROFILE_BIND(m, e, N)
     real* ye = y + (size_t)e * RMT_V * N;
     const real h = real(h_), hh = real(0.5 * h_), h6 = real(h_ / 6.0);
     rmt_flags_t flag;
@@ -770,6 +776,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk4_mem(
                 carry.P = s_c.P[s];
 #pragma unroll
                 for (int i = 0; i < RMT_V; ++i) carry.up[i] = s_c.up[s][i];
+                RMT_PROFILE_AT(carry, base)
 #if RMT_FORCING
                 rmt_forcing_apply3(m, members + (size_t)e * RMT_NM, tstep + rmt_rk4_c(s) * h_);    // the wall temperature of this stage (the inlet: s_c)
 #endif

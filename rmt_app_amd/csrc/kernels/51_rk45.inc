@@ -68,6 +68,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_mem(
     const int e = blockIdx.x;
     RmtMember m;
     rmt_load_member(members + (size_t)e * RMT_NM, m);
+    RMT_PROFILE_BIND(m, e, N)
     const size_t per = (size_t)RMT_V * N, tot = per * E;
     real* ye = y + e * per;
     real* wk = work + e * per;                  // workspace slots j*tot: K_j when they do not fit in LDS
@@ -135,6 +136,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_mem(
                     carry.P = s_c.P[s];
 #pragma unroll
                     for (int i = 0; i < RMT_V; ++i) carry.up[i] = s_c.up[s][i];
+                    RMT_PROFILE_AT(carry, base)
 #if RMT_FORCING
                     rmt_forcing_apply3(m, members + (size_t)e * RMT_NM, t + rmt_dp_c(s) * h);    // the wall temperature of this stage (the inlet: s_c)
 #endif
@@ -323,8 +325,10 @@ __device__ __forceinline__ void rmt_rk45_onchip(
                                              (threadIdx.x < RMT_S ? M_CIN + (int)threadIdx.x : M_THETA_IN)]);
     RmtMember m;
     rmt_load_member(members + (size_t)e * RMT_NM, m);
+    RMT_PROFILE_BIND(m, e, N)
     RmtCarry carry;
     rmt_carry_inlet(m, carry);
+    RMT_PROFILE_AT(carry, gnode0 - node0)
     real* ye = y + (size_t)e * RMT_V * N;
     int nvalid = N - gnode0;
     nvalid = nvalid < 0 ? 0 : (nvalid > RMT_NPT ? RMT_NPT : nvalid);
@@ -624,6 +628,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_reg(
 // of one message latency per chunk; after stage 7 the running maximum of the error norm travels the same way and
 // the last chunk publishes the reactor's norm in the team's decision slot.  A step costs 7 stage times + the
 // skew + one decision round trip instead of the memory-resident stepper's walk over all node blocks on ONE CU.
+#if !RMT_PROFILE      // (a profiled run keeps a reactor on one workgroup: the chained form does not carry the profile)
 extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_chain(
         real* __restrict__ y, const double* __restrict__ members, const int N, const int E, const int C,
         const int T, const double t0, const double t1, const double rtol, const double atol, const double h0,
@@ -667,5 +672,6 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_rk45_chain(
         for (int e2 = e; e2 < E; e2 += T) atomicOr(&flags[e2], RMT_FLAG_STEP);    // (the one in flight has it: t < t1)
     }
 }
+#endif   // !RMT_PROFILE
 #endif   // on-chip RK45 fits
 

@@ -6,6 +6,7 @@
 //   K3,K2 <- K2,K1; K1 = f(y_i); y_{i+1} = y_i + h(23K1-16K2+5K3)/12            [AB3 / predictor]
 //   K0 = f(y_{i+1}); y_{i+1} = y_i + h(9K0+19K1-5K2+K3)/24                      [PreCorr3 only]
 // work = 8 arrays [E][V][N]: RK4 scratch (3), K ring (3), K0, predictor.
+#if !RMT_PROFILE      // (the host refuses the multistep methods for a profiled run: the kernel does not carry the profile)
 __device__ __forceinline__ void rmt_eval_mem(const RmtMember& m, RmtShared& sh, int& ph,
                                              const real* src, real* dst,   // may alias (in-place)
                                              const int N, rmt_flags_t& flag) {
@@ -130,4 +131,5 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK) void rmt_n2_multistep_mem(
     lflag |= rmt_flags_bits(flag);
     if (lflag) atomicOr(&flags[e], lflag);
 }
+#endif   // !RMT_PROFILE
 

@@ -195,6 +195,7 @@ __device__ __forceinline__ void rmt_ros_stage(const RmtMember& m, RmtShared& sh,
         unsigned mk = 0u;
         if (STAGE <= 3) {
             RmtLocal lc[1];
+            RMT_PROFILE_AT(carry, base)
             rmt_rhs_block<1, true, false>(m, sh, ph, ys, valid ? 1 : 0, carry, k, flag, nullptr,
                                           STAGE == 1 ? lc : nullptr);
             ph ^= 1;
@@ -209,6 +210,7 @@ __device__ __forceinline__ void rmt_ros_stage(const RmtMember& m, RmtShared& sh,
                     RmtNode ndj;
                     real rj[RMT_R];
                     (void)rmt_node_pre(m, ys[0], ndj);
+                    RMT_PROFILE_NODE(m, ndj, node)
                     rmt_node_jac(m, ndj, ys[0], lc[0].P, a, rj, scratch_flag);
                 }
 #else
@@ -222,6 +224,7 @@ __device__ __forceinline__ void rmt_ros_stage(const RmtMember& m, RmtShared& sh,
                     const real id = rmt_rcp(yp[c] - ys[0][c]);
                     RmtNode ndp;
                     (void)rmt_node_pre(m, yp, ndp);
+                    RMT_PROFILE_NODE(m, ndp, node)
                     rmt_node_post(m, ndp, yp, lc[0].up, lc[0].P, kp, scratch_flag);
 #pragma unroll
                     for (int r = 0; r < RMT_V; ++r) a[r][c] = -(kp[r] - k[0][r]) * id;
@@ -438,6 +441,7 @@ __device__ __forceinline__ void rmt_rodas_bs(const RmtMember& RMT_M_ARG, RmtShar
     real xc[RMT_V];
 #pragma unroll
     for (int i = 0; i < RMT_V; ++i) { carry.up[i] = rc.up[STAGE - 1][i]; xc[i] = rc.xc[STAGE - 1][i]; }
+    RMT_PROFILE_AT(carry, node - tid)                    // the block's first node
     RmtLocal lc[1];
     // Python-exception tests on stage 1 (f at the accepted state y_n) like the explicit steppers; the later
     // stages are evaluated test-free unless RMT_CHECK_ALL_STAGES (a failure there still ends non-finite -> rejected)
@@ -479,6 +483,7 @@ __device__ __forceinline__ void rmt_rodas_bs(const RmtMember& RMT_M_ARG, RmtShar
             const real id = rmt_rcp(yp[c] - ys[0][c]);
             RmtNode ndp;
             (void)rmt_node_pre(m, yp, ndp);
+            RMT_PROFILE_NODE(m, ndp, node)
             rmt_node_post(m, ndp, yp, lc[0].up, lc[0].P, kp, scratch_flag);
 #pragma unroll
             for (int r = 0; r < RMT_V; ++r) a[r][c] = -(kp[r] - k[0][r]) * id;
@@ -730,6 +735,7 @@ __device__ __forceinline__ void rmt_rodas_blocks(const RmtMember& m, RmtShared& 
             real ysd[1][RMT_V], kd[1][RMT_V];
 #pragma unroll
             for (int i = 0; i < RMT_V; ++i) { carry.up[i] = rc.up[6][i]; ysd[0][i] = y0[i]; }
+            RMT_PROFILE_AT(carry, base)
             rmt_noflags_t nof_ft;
             rmt_rhs_block<1, true, 0>(md, sh, ph, ysd, valid ? 1 : 0, carry, kd, nof_ft);
             ph ^= 1;
@@ -783,6 +789,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ro
     const int e = blockIdx.x;
     RmtMember m;
     rmt_load_member(members + (size_t)e * RMT_NM, m);
+    RMT_PROFILE_BIND(m, e, N)
     const size_t per = (size_t)RMT_V * N, tot = per * E;
     real* ye = y + e * per;
     real* F = work + 0 * tot + e * per;
@@ -927,7 +934,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ro
 // decision slot, every chunk reads it and applies the same controller arithmetic, so t, h and the
 // accept/reject history stay identical in all chunks without any other synchronisation.
 // A step costs 6 stage times + the pipeline skew instead of 6 C stage times.
-#if !RMT_FORCING       // (a forced run keeps a reactor on one workgroup: the host selects rmt_n2_ros4_mem)
+#if !RMT_FORCING && !RMT_PROFILE       // (a forced or profiled run keeps a reactor on one workgroup: the host selects rmt_n2_ros4_mem)
 extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ros4_chain(
         real* __restrict__ y, real* __restrict__ work, const double* __restrict__ members, const int N,
         const int E, const int C, const int T, const int W, const double t0, const double t1,
@@ -1102,7 +1109,7 @@ extern "C" __global__ __launch_bounds__(RMT_BLOCK, RMT_ROS_WAVES) void rmt_n2_ro
         for (int e2 = e; e2 < E; e2 += T) atomicOr(&flags[e2], RMT_FLAG_STEP);
     }
 }
-#endif   // !RMT_FORCING
+#endif   // !RMT_FORCING && !RMT_PROFILE
 #endif   // RODAS4
 #endif   // !RMT_ROS_QUAD
 

@@ -42,6 +42,10 @@ __device__ __forceinline__ preal rmt_steady_eval(const RmtMember& m, const real*
                                                  real (&a)[RMT_V][RMT_V], FL& fl) {
     RmtNode nd;
     const preal az = rmt_node_pre(m, y, nd);
+#if RMT_PROFILE
+    nd.act = m.act;                   // the node this lane is solving (the kernel below reads the table per node)
+    nd.dtm = m.dtm;
+#endif
     real r[RMT_R];
     rmt_node_jac(m, nd, y, P, a, r, fl);
     rmt_node_post<FL, true>(m, nd, y, up, P, f, fl, r);
@@ -179,6 +183,7 @@ extern "C" __global__ __launch_bounds__(64) void rmt_n2_steady_march(
     const bool live = e < E;
     RmtMember m;
     rmt_load_member(members + (size_t)(live ? e : 0) * RMT_NM, m);      // dead lanes read member 0 and write nothing
+    RMT_PROFILE_BIND(m, live ? e : 0, N)
     real up[RMT_V], yz[RMT_V];
 #pragma unroll
     for (int i = 0; i < RMT_S; ++i) up[i] = rmt_max(m.cin[i], RMT_EPS);
@@ -198,6 +203,10 @@ extern "C" __global__ __launch_bounds__(64) void rmt_n2_steady_march(
         if (active) {
 #pragma unroll
             for (int i = 0; i < RMT_V; ++i) yz[i] = up[i];
+#if RMT_PROFILE
+            m.act = real(m.prof[z]);                      // (active: z < N)
+            m.dtm = real(m.prof[N + z]);
+#endif
             const RmtSteadyNode nd = rmt_steady_node(m, up, P, yz, tol, max_iter, flag);
             itmax = nd.iters > itmax ? (long long)nd.iters : itmax;
             ndamped += nd.rejected > 0 ? 1 : 0;

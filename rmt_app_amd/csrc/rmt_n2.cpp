@@ -88,7 +88,19 @@ struct rmt_n2_handle {
     int plain_left = 0;
     bool timed = false;
     int last_chunks = 1, last_teams = 0;     // geometry of the last stepper launch (rmt_n2_last_geometry)
+    // axial profiles (code objects generated with RMT_PROFILE): the table [E][2][N] and the module's pointer to it
+    int profiled = 0;
+    double* d_profile = nullptr;
+    hipDeviceptr_t profile_slot = nullptr;   // address of the module's `rmt_profile_tab`
 };
+
+// a profiled handle launches nothing before its table is there (the kernels would read through a null pointer)
+#define PROFILE_READY(h)                                                                    \
+    do {                                                                                    \
+        if ((h)->profiled && !(h)->d_profile)                                               \
+            return fail("this handle's code object was generated with RMT_PROFILE: call rmt_n2_set_profile before the "  \
+                        "first launch");                                                    \
+    } while (0)
 
 // bytes of the member rows [E][RMT_N2_MEMBER_FIXED + S + NU] and of one state [E][V][N]
 static size_t member_bytes(const rmt_n2_handle* h) { return (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double); }
@@ -205,6 +217,8 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
     if (p->ros4_nodes_per_block != 0 && p->ros4_nodes_per_block != p->block && p->ros4_nodes_per_block * 4 != p->block)
         return fail("ros4_nodes_per_block must be 0, block or block / 4 (got %d for block %d)", p->ros4_nodes_per_block, p->block);
     if (!p->code_object || !p->code_size || !p->members) return fail("plan lacks code object/members");
+    if (p->profiled != 0 && p->profiled != 1) return fail("plan.profiled must be 0 or 1 (got %d)", p->profiled);
+    if (p->profiled && p->fp32) return fail("profiled code objects (RMT_PROFILE) are fp64 only");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail("no HIP device available: the N2 integrator has no CPU fallback");
@@ -219,6 +233,7 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
     h->block = p->block;
     h->npt = p->nodes_per_thread;
     h->real_size = p->fp32 ? 4 : 8;
+    h->profiled = p->profiled;
 #define CREATE_OK(call)                                                                     \
     do {                                                                                    \
         hipError_t e_ = (call);                                                             \
@@ -259,6 +274,16 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
         return 1;
     }
     (void)hipGetLastError();
+    if (h->profiled) {
+        size_t bytes = 0;
+        const hipError_t e = hipModuleGetGlobal(&h->profile_slot, &bytes, h->module, "rmt_profile_tab");
+        if (e != hipSuccess || bytes != sizeof(double*)) {
+            fail("plan.profiled = 1, but the code object has no rmt_profile_tab (generate it with RMT_PROFILE 1): %s",
+                 hipGetErrorString(e));
+            rmt_n2_destroy(h);
+            return 1;
+        }
+    }
     CREATE_OK(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device));
     const size_t mbytes = member_bytes(h);
     CREATE_OK(hipMalloc((void**)&h->d_members, mbytes));
@@ -283,6 +308,7 @@ extern "C" void rmt_n2_destroy(rmt_n2_handle* h) {
     DeviceGuard guard_(h);
     if (h->fb_pending && h->ev_fb) (void)hipEventSynchronize(h->ev_fb);       // the counter copy into fb_host has landed
     if (h->d_members) (void)hipFree(h->d_members);
+    if (h->d_profile) (void)hipFree(h->d_profile);
     if (h->d_flags) (void)hipFree(h->d_flags);
     if (h->d_work) (void)hipFree(h->d_work);
     if (h->d_backup) (void)hipFree(h->d_backup);
@@ -336,6 +362,27 @@ extern "C" int rmt_n2_get_members(rmt_n2_handle* h, double* members) {
     const size_t mbytes = member_bytes(h);
     HIP_OK(hipMemcpyAsync(members, h->d_members, mbytes, hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int rmt_n2_set_profile(rmt_n2_handle* h, const double* table_host) {
+    if (!h || !table_host) return fail("null argument");
+    if (!h->profiled)
+        return fail("rmt_n2_set_profile: this handle's code object was not generated with RMT_PROFILE (plan.profiled = 0)");
+    ON_DEVICE(h);
+    const size_t bytes = (size_t)h->E * 2 * (size_t)h->N * sizeof(double);
+    // (a launch in flight may still read the old values: wait for it, then ONE blocking upload into the same buffer)
+    HIP_OK(hipStreamSynchronize(h->stream));
+    double* buf = h->d_profile;
+    if (!buf) HIP_OK(hipMalloc((void**)&buf, bytes));
+    hipError_t e = hipMemcpy(buf, table_host, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpyHtoD(h->profile_slot, &buf, sizeof buf);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (!h->d_profile) (void)hipFree(buf);
+        return fail("rmt_n2_set_profile: %s", hipGetErrorString(e));
+    }
+    h->d_profile = buf;
     return 0;
 }
 
@@ -405,6 +452,7 @@ extern "C" int rmt_n2_last_kernel_ms(rmt_n2_handle* h, float* ms) {
 extern "C" int rmt_n2_rhs(rmt_n2_handle* h, double t, const void* y, void* dydt) {
     (void)t; /* the N2 right-hand side is autonomous (pbHomoReactor.py:3706: t unused) */
     if (!h || !y || !dydt) return fail("null argument");
+    PROFILE_READY(h);
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     void* args[] = {(void*)&y, (void*)&dydt, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&h->d_flags};
@@ -453,6 +501,7 @@ extern "C" int rmt_n2_rk4(rmt_n2_handle* h, void* y, double t0, double dt, int64
     (void)t0;
     if (!h || !y) return fail("null argument");
     if (!(dt > 0) || nsteps < 0) return fail("rk4 needs dt > 0 and nsteps >= 0");
+    PROFILE_READY(h);
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     long long ns = (long long)nsteps;
@@ -552,6 +601,7 @@ extern "C" int rmt_n2_multistep(rmt_n2_handle* h, void* y, double t0, double dt,
     if (!(dt > 0) || nsteps < 3) return fail("multistep needs dt > 0 and nsteps >= 3");
     if (method != 0 && method != 1) return fail("method must be 0 (AdBash3) or 1 (PreCorr3)");
     if (!h->f_multistep) return fail("code object has no multistep kernel");
+    PROFILE_READY(h);
     ON_DEVICE(h);
     if (ensure_work(h, 8)) return 1;
     int N = h->N, E = h->E;
@@ -565,6 +615,7 @@ extern "C" int rmt_n2_rk45(rmt_n2_handle* h, void* y, double t0, double t1, doub
                            double h0, int64_t max_steps, rmt_n2_stats* stats) {
     if (!h || !y || !stats) return fail("null argument");
     if (!(t1 > t0) || !(rtol > 0) || !(atol >= 0) || !(h0 != 0)) return fail("bad rk45 arguments");
+    PROFILE_READY(h);
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     long long ms = (long long)max_steps;
@@ -610,6 +661,7 @@ extern "C" int rmt_n2_ros4(rmt_n2_handle* h, void* y, double t0, double t1, doub
     if (!h || !y || !stats) return fail("null argument");
     if (!(t1 > t0) || !(rtol > 0) || !(atol >= 0) || !(h0 != 0)) return fail("bad ros4 arguments");
     if (!h->f_ros4) return fail("code object has no ros4 kernel");
+    PROFILE_READY(h);
     ON_DEVICE(h);
     if (h->block > 512)
         return fail("the Rosenbrock kernel holds a VxV matrix per lane: generate the code object with "
@@ -688,6 +740,7 @@ extern "C" int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* ou
     if (!h || !members1 || !out || !stats) return fail("null argument");
     if (nout < 2 || !(rtol > 0) || !(atol >= 0) || !(h0 > 0)) return fail("bad N1 arguments");
     if (!h->f_n1) return fail("code object has no N1 kernel");
+    PROFILE_READY(h);
     ON_DEVICE(h);
     const size_t mbytes = member_bytes(h);
     if (!h->d_members1) HIP_OK(hipMalloc((void**)&h->d_members1, mbytes));
@@ -709,6 +762,7 @@ extern "C" int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, in
     if (!(tol > 0) || max_iter < 1) return fail("bad steady-march arguments (tolerance > 0, max_iter >= 1)");
     if (!h->f_march) return fail("code object has no rmt_n2_steady_march (generate it with RMT_WITH_MARCH)");
     if (h->fp32) return fail("the steady-state march is fp64 only");
+    PROFILE_READY(h);
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     long long mi = (long long)max_iter;

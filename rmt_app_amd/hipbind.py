@@ -30,7 +30,7 @@ class Plan(C.Structure):
         ("abi_version", C.c_int32), ("n_species", C.c_int32), ("n_reactions", C.c_int32),
         ("n_vars", C.c_int32), ("n_nodes", C.c_int32), ("n_members", C.c_int32),
         ("fp32", C.c_int32), ("block", C.c_int32), ("nodes_per_thread", C.c_int32),
-        ("n_user_params", C.c_int32), ("ros4_nodes_per_block", C.c_int32), ("reserved", C.c_int32),
+        ("n_user_params", C.c_int32), ("ros4_nodes_per_block", C.c_int32), ("profiled", C.c_int32),
         ("code_object", C.c_void_p), ("code_size", C.c_size_t), ("members", C.POINTER(C.c_double)),
     ]
 
@@ -66,6 +66,7 @@ def lib():
     L.rmt_n2_set_members.argtypes = [vp, C.POINTER(dbl)]
     L.rmt_n2_set_members_async.argtypes = [vp, vp]
     L.rmt_n2_get_members.argtypes = [vp, C.POINTER(dbl)]
+    L.rmt_n2_set_profile.argtypes = [vp, C.POINTER(dbl)]
     L.rmt_n2_rhs.argtypes = [vp, dbl, vp, vp]
     L.rmt_n2_rk4.argtypes = [vp, vp, dbl, dbl, i64]
     L.rmt_n2_multistep.argtypes = [vp, vp, dbl, dbl, i64, C.c_int]

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from . import control, hipbind, initial, launches, monitor, plan, schedule
+from . import control, hipbind, initial, launches, monitor, plan, profile, schedule
 from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
@@ -137,6 +137,12 @@ def forced_tail(defines, S):
     return schedule.TAIL + int(S) if level == "2" else schedule.TAIL if level == "1" else 0
 
 
+def is_profiled(defines):
+    """True for the prelude defines of a code object that reads an axial profile (csrc/kernels/12_profile.inc): its handle
+    needs the table of rmt_n2_set_profile, and it holds no chained kernel."""
+    return str((defines or {}).get(profile.DEFINE, "0")) == "1"
+
+
 def forced_literals(member_defines, level="1"):
     """The sweep-invariant member fields a FORCED code object may take as literals: all but the ones the schedule moves -
     three for RMT_FORCING 1, the inlet composition as well for RMT_FORCING 2 (``level``) - no RMT_MC_* literal may freeze a
@@ -145,14 +151,15 @@ def forced_literals(member_defines, level="1"):
     return {k: v for k, v in member_defines.items() if k not in moved}
 
 
-def forced_mode(ivp, N, block, npt, want=None):
+def forced_mode(ivp, N, block, npt, want=None, key="schedule", what="forcing"):
     """The kernel form of a forced launch, set by the HOST (rmt_n2_set_mode): the chained forms do not carry the forcing,
-    so the library's auto mode must not pick them.  "reg" (the on-chip steppers) when the reactor fits one workgroup,
+    so the library's auto mode must not pick them.  The same rule serves profiled runs (``key`` "axial-profile", ``what``
+    "profile"), forced or not.  "reg" (the on-chip steppers) when the reactor fits one workgroup,
     else "mem"; the stiff stepper always runs rmt_n2_ros4_mem (any N on one workgroup).  `want`: solver-config
     "device-mode"."""
     if want not in (None, "auto", "reg", "mem"):
-        raise ValueError("solver-config 'device-mode' must be 'reg' or 'mem' together with 'schedule' (got %r): the "
-                         "chained kernels do not carry the forcing" % (want,))
+        raise ValueError("solver-config 'device-mode' must be 'reg' or 'mem' together with '%s' (got %r): the "
+                         "chained kernels do not carry the %s" % (key, want, what))
     if ivp == "hip-ros4":
         return "mem"
     fits = int(N) <= int(block)*int(npt)
@@ -192,6 +199,8 @@ def kcache_choice(mech, N, fp32, block, npt, lds_state, defines):
     chained = int(N) > int(block)*int(npt)
     if is_forced(defs) and (chained or os.environ.get("RMT_N2_FORCED_PLAIN")):
         return defs, lds_state       # (a forced reactor beyond one workgroup runs the memory-resident form, never the chain)
+    if is_profiled(defs) and (chained or os.environ.get("RMT_N2_PROFILED_PLAIN")):
+        return defs, lds_state       # (the same for a profiled one: a profiled unit has no chained kernel)
     key = "RMT_KCACHE_CHAIN" if chained else "RMT_KCACHE"
     geo = (int(block), int(npt))
     model = getattr(mech, "model", "N2")
@@ -308,6 +317,8 @@ def march_plan(mech, N, defines=None, rows=None):
     defs = {"RMT_KCACHE": "0", "RMT_KCACHE_CHAIN": "0"}
     if is_forced(defines):
         defs["RMT_FORCING"] = forcing_level(defines)
+    if is_profiled(defines):          # (the march reads the table for the node it is solving)
+        defs[profile.DEFINE] = "1"
     return code_plan(mech, N, False, None, MARCH_BLOCK, 1, None, defs, ("march",), rows, specialize=False)
 
 
@@ -425,8 +436,13 @@ class N2Device:
 
     def __init__(self, mech, members, N, fp32=False, block=None, npt=None, device=None,
                  extra_opts="", lds_state=None, defines=None, code=None, specialize=None,
-                 features=()):
+                 features=(), profile=None):
+        """``profile``: the table [E][2][N] of an axial profile (profile.Profile.table: per member the catalyst activities,
+        then the coolant offsets).  The code object is generated with RMT_PROFILE and the table uploaded before anything
+        is launched.  (``defines={"RMT_PROFILE": "1"}`` alone creates the profiled device without a table: set_profile.)"""
         torch = _torch()
+        if profile is not None:
+            defines = {**(defines or {}), "RMT_PROFILE": "1"}
         self.torch = torch
         self.mech, self.N, self.fp32 = mech, int(N), bool(fp32)
         members = np.ascontiguousarray(members, dtype=np.float64)
@@ -454,6 +470,8 @@ class N2Device:
         p.n_user_params = self.row_width - plan.MEMBER_FIXED - mech.S       # (a forced row's tail travels as 4 or 4 + S more)
         self.ros_quad = str(self.defines.get("RMT_ROS_QUAD", "0")) == "1"
         p.ros4_nodes_per_block = self.block//4 if self.ros_quad else 0
+        self.profiled = is_profiled(self.defines)
+        p.profiled = int(self.profiled)
         p.code_object = C.cast(self._code, C.c_void_p)
         p.code_size = len(code)
         p.members = members.ctypes.data_as(C.POINTER(C.c_double))
@@ -470,6 +488,13 @@ class N2Device:
         self._stats = torch.zeros((self.E, 4), dtype=torch.float64, device=self.device)
         self.march = None       # a second device of the same rows with the steady-state march (attach_march)
         self.use_current_stream()
+        self.profile = None
+        if profile is not None:
+            try:
+                self.set_profile(profile)
+            except Exception:
+                self.close()
+                raise
 
     # -- plumbing
     def use_current_stream(self):
@@ -500,6 +525,18 @@ class N2Device:
         self.members = members
         hipbind.check(hipbind.lib().rmt_n2_set_members_async(self.h, C.c_void_p(pinned.data_ptr())))
         return pinned
+
+    def set_profile(self, table):
+        """Upload the axial profile [E][2][N] (rmt_n2_set_profile: one synchronous copy, before the first launch).  Only
+        for a device whose code object was generated with RMT_PROFILE."""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.shape != (self.E, 2, self.N):
+            raise hipbind.RmtN2Error("the profile table must be [E][2][N] = %r doubles (got %r)"
+                                     % ((self.E, 2, self.N), table.shape))
+        hipbind.check(hipbind.lib().rmt_n2_set_profile(self.h, table.ctypes.data_as(C.POINTER(C.c_double))))
+        self.profile = table
+        if self.march is not None:
+            self.march.set_profile(table)
 
     def get_members(self):
         """The device rows as they are now [E][row_width] (synchronises the stream): what the last refresh uploaded and
@@ -611,7 +648,7 @@ class N2Device:
                 raise hipbind.RmtN2Error("the steady-state march is for model N2 in fp64")
             cp = march_plan(self.mech, self.N, self.defines, self.members)
             self.march = N2Device(self.mech, self.members, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
-                                  defines=cp.defines, specialize=False, features=cp.features)
+                                  defines=cp.defines, specialize=False, features=cp.features, profile=self.profile)
         return self
 
     def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
@@ -951,7 +988,7 @@ def mechanism_for(modelInput, inputs, cfg):
 
 
 def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=None, npt=None, defines=None,
-                 features=(), forcing=None, march=False):
+                 features=(), forcing=None, march=False, prof=None):
     """Device + initial state for the members THIS process integrates.
 
     Single process: all of ``inputs``.  As one rank of a torch.distributed job (``sync``, see
@@ -961,7 +998,12 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     ``forcing`` (a Forcing, solver-config "schedule"): the code object is generated with RMT_FORCING (2 when the schedule
     moves the feed composition, else 1), the rows get their tail, and the host fixes the kernel form (forced_mode).
     ``march`` (solver-config "initial", single process): a second handle on the same rows holds the steady-state march
-    (N2Device.attach_march)."""
+    (N2Device.attach_march).
+    ``prof`` (a profile.Profile, solver-config "axial-profile", single process): the code object is generated with
+    RMT_PROFILE, the table is uploaded before anything is launched, and the host fixes the kernel form by the rule of the
+    forced runs (no chained form carries the profile)."""
+    if prof is not None and sync is not None:
+        raise NotImplementedError("solver-config 'axial-profile' is not available in a multi-rank run")
     if march and sync is not None:
         raise NotImplementedError("solver-config 'initial' is not available in a multi-rank run")
     if forcing is not None:
@@ -972,9 +1014,15 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
         IV = plan.initial_states([nm for nm, _ in pairs], mech, zNo, init)
         if forcing is not None:
             rows = forcing.attach(rows, [nm for nm, _ in pairs])
-        dev = device_cls()(mech, rows, zNo, fp32=fp32, block=block, npt=npt, defines=defines, features=features)
+        extra = {} if prof is None else {"profile": prof.table()}
+        dev = device_cls()(mech, rows, zNo, fp32=fp32, block=block, npt=npt, defines=defines, features=features, **extra)
         if forcing is not None:
             forcing.fix_mode(dev, "hip-ros4" if "ros4" in features else "explicit")
+        elif prof is not None:
+            prof.modes["ros4" if "ros4" in features else "explicit"] = mode = forced_mode(
+                "hip-ros4" if "ros4" in features else "explicit", zNo, dev.block, dev.npt, prof.want_mode,
+                "axial-profile", "profile")
+            dev.set_mode(mode)
         if march:
             try:
                 dev.attach_march()
@@ -1006,20 +1054,21 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     return dev, ens.named, ens.IV
 
 
-def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None, forcing=None, march=False):
+def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None, forcing=None, march=False,
+              prof=None):
     """The two devices of ivp "hip-auto" (explicit pair in its on-chip geometry, Rosenbrock family) behind one
     AutoStepper; an explicit `block` / `nodes-per-thread` of the solver-config applies to the explicit device."""
-    if block is None and forcing is not None:       # (no chained chunks: they do not carry the forcing)
+    if block is None and (forcing is not None or prof is not None):       # (no chained chunks: they carry neither)
         b45, n45, d45 = rk45_geometry(mech.V, zNo, fp32, chain=False)
     elif block is None:
         b45, n45, d45 = rk45_geometry(mech.V, zNo, fp32, E=len(inputs) if sync is None else max(sync.counts))
     else:
         b45, n45, d45 = block, npt, {}
     dev45, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=b45, npt=n45,
-                                          defines={**(defines or {}), **d45}, forcing=forcing, march=march)
+                                          defines={**(defines or {}), **d45}, forcing=forcing, march=march, prof=prof)
     def make_ros4():
         return open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=ros4_block(mech.V, zNo, fp32),
-                            npt=1, defines=defines, features=("ros4",), forcing=forcing)[0]
+                            npt=1, defines=defines, features=("ros4",), forcing=forcing, prof=prof)[0]
     if sync is None:
         return AutoStepper(dev45, make_ros4), named_local, IV       # built only if the problem turns out stiff
     try:        # multi-rank: creation involves collectives and the ranks may decide differently -> build it now
@@ -1373,6 +1422,10 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
     # "initial": where the run starts (initial.py); absent = None = the reference's cold start, exactly the run without it
     ini = initial.parse(modelInput, sync is not None) if with_schedule else None
+    # "axial-profile": catalyst activity and coolant zones along the bed (profile.py); absent = None = exactly the run
+    # without it
+    profile.check_model(modelInput)
+    prof = profile.parse(modelInput, members_inputs, ivp, sync is not None) if with_schedule else None
     # the ONE launch list of the run; a sample that fell on a mark carries that mark's time from here on (result entries)
     walk, sample_times, control_times = launches.merge(
         opT, tNo, forced_by.times if forced_by is not None else (), mon.times if mon is not None else None,
@@ -1392,19 +1445,28 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         if ivp == "hip-rk4" and block is None:
             # the geometry of ONE workgroup per reactor (no chunks: the chained kernels do not carry the forcing)
             block, npt = choose_geometry(zNo, mech.V, fp32)
+    if prof is not None:
+        if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
+            raise NotImplementedError("solver-config 'axial-profile' with the stiff stepper needs a mechanism of at most 8 "
+                                      "variables per node (this one has %d): its four-lane form does not carry the "
+                                      "profile - use ivp 'hip-rk45' or 'hip-rk4'" % mech.V)
+        prof.want_mode, prof.modes = cfg.get('device-mode'), {}
+        if ivp == "hip-rk4" and block is None:          # ONE workgroup per reactor, as for a forced run
+            block, npt = choose_geometry(zNo, mech.V, fp32)
     if ivp == "hip-ros4" and block is None:
         block, npt = ros4_block(mech.V, zNo, fp32, ros4_quad(mech, fp32)), 1
     defines = dict(defines or {})
     if ivp == "hip-rk45" and block is None:
-        block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, **({"chain": False} if forcing is not None else {"E": E_gpu}))
+        block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, **({"chain": False} if forcing is not None or prof is not None
+                                                                 else {"E": E_gpu}))
         defines.update(geo_defs)
     if ivp == "hip-auto":
         dev, named_local, IV = open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block, npt, forcing=forcing,
-                                         march=ini is not None)
+                                         march=ini is not None, prof=prof)
     else:
         dev, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=block, npt=npt,
                                             defines=defines, features=("ros4",) if ivp == "hip-ros4" else (),
-                                            forcing=forcing, march=ini is not None)
+                                            forcing=forcing, march=ini is not None, prof=prof)
     # the process that returns the results (rank 0, or the only one) packs EVERY member
     packer = sync is None or sync.rank == 0
     try:
@@ -1433,6 +1495,9 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
             stats["device-mode"] = dict(forcing.modes)
             stats.setdefault("launches", len(walk))            # (a monitored or controlled run has it already)
             stats["last-geometry"] = dev.last_geometry()
+        elif prof is not None:
+            stats["device-mode"] = dict(prof.modes)
+            stats["last-geometry"] = dev.last_geometry()
     finally:
         dev.close()
     res = result(packs[0] if packs else [], modelInput, zNo, opTSpan)
@@ -1449,6 +1514,11 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         if members_inputs:
             for entry, c in zip(res["ensemble"], entries):
                 entry["control"] = c
+    if prof is not None:
+        res["axial-profile"] = profile.result_entry(prof, 0)
+        if members_inputs:
+            for e, entry in enumerate(res["ensemble"]):
+                entry["axial-profile"] = profile.result_entry(prof, e)
     if started is not None:
         res["initial"] = started[0]
         if members_inputs:

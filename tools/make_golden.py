@@ -5,11 +5,12 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
 coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
 closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|syn12]: discrete steady states of model N2,
-G17 - like G13..G15 it runs SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
+G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18 - like G13..G15 these
+run SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
 """
@@ -1272,6 +1273,174 @@ def g_steady_state(which=None):
         print("G17 %s written: max|f| = %.3e after %.0f s (LSODA alone %.3e)" % (name, r, t, r_ode), flush=True)
 
 
+# ------------------------------------------------------------------ G18: axial profiles of model N2
+# (solver-config "axial-profile", rmt_app_amd/profile.py): catalyst activity a(z) on every reaction rate, coolant
+# temperature Tm(z) in the wall term.  The oracle does not change: the activity wraps every entry of pr["RATES"] in a
+# closure (vectorised_kinetics rebinds the user lambda through the closure cell and broadcasts the node array), and the
+# coolant uses that the right-hand side is affine in Tm - pr["Tm"] must stay a scalar (make_local_rhs tests pr["Tm"] == 0)
+# - so f(Tm(z)) = f0 + (f1 - f0) delta(z) on the temperature row, f0 / f1 evaluated at MeTe and MeTe + 1.  Against
+# rhs_loop node by node with scalar a_z and Tm(z_n) the two agree to 2.1e-15 relative (DME, 20 nodes).  Nothing of the
+# product is imported: the node rule (z_n = n/(N-1), right-continuous at a repeated position) is restated below.
+G18_BED_A = {"position": [0.0, 0.3, 0.3, 0.5, 0.5, 1.0], "catalyst-activity": [0.4, 0.4, 1.0, 1.0, 1.0, 1.0],
+             "medium-temperature": [533.0, 533.0, 533.0, 533.0, 513.0, 513.0]}
+G18_CASES = {
+    "A": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2, "axial-profile": G18_BED_A},
+    "B": {"input": "dme_nb", "process-type": "iso-thermal", "zNo": 20, "period": 0.4, "tNo": 2,
+          "axial-profile": {"position": [0.0, 0.5, 1.0], "catalyst-activity": [0.0, 1.0, 1.0]}},
+    "C": {"input": "dme_nb", "zNo": 600, "period": 0.06, "tNo": 3, "method": "DOP853",
+          "axial-profile": {"position": [0.0, 0.4, 0.4, 1.0], "catalyst-activity": [0.5, 0.5, 1.0, 1.0],
+                            "medium-temperature": [533.0, 525.0, 525.0, 513.0]}},
+    "AS": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2, "axial-profile": G18_BED_A,
+           "schedule": {"time": [0.0, 0.2, 0.2, 0.4], "medium-temperature": [523.0, 523.0, 533.0, 533.0]}},
+    "A0": {"input": "dme_nb", "zNo": 20, "period": 0.4, "tNo": 2},                         # the plain twin of A
+    "C0": {"input": "dme_nb", "zNo": 600, "period": 0.06, "tNo": 3, "method": "DOP853"},   # the plain twin of C
+    "S": {"input": "dme_nb", "zNo": 20, "axial-profile": G18_BED_A, "steady": True},
+}
+
+
+def g18_nodes(position, values, N):
+    """the piecewise-linear function at z_n = n/(N-1): right-continuous at a jump, the last value at z = 1"""
+    p, v = np.asarray(position, dtype=float), np.asarray(values, dtype=float)
+    out = np.zeros(N)
+    for n in range(N):
+        z = n/float(N - 1)
+        k = int(np.searchsorted(p, z, side="right")) - 1
+        out[n] = v[-1] if k >= len(p) - 1 else v[k] + (v[k + 1] - v[k])*(z - p[k])/(p[k + 1] - p[k])
+    return out
+
+
+def g18_profiled_pr(pr, a):
+    """pr with every rate multiplied by the node array a [N]"""
+    def wrap(f, a):
+        return lambda x: a*f(x)
+    out = dict(pr)
+    out["RATES"] = {k: wrap(f, a) for k, f in pr["RATES"].items()}
+    return out
+
+
+def g18_profiled_rhs(O, pr, a, delta):
+    """(f(t, y), the two parameter dicts whose "Tm" a schedule moves together) of the profiled bed"""
+    p0 = g18_profiled_pr(pr, np.asarray(a, dtype=float))
+    p1 = dict(p0)
+    f0, f1 = O.make_rhs_vec(p0), O.make_rhs_vec(p1)
+    S, N, V = pr["compNo"], pr["zNo"], pr["varNo"]
+    delta = np.asarray(delta, dtype=float)
+    if pr["iso"] or pr["Tm"] == 0 or not np.any(delta != 0):
+        return f0, (p0,)
+
+    def f(t, y):
+        p1["Tm"] = p0["Tm"] + 1.0
+        r0 = np.array(f0(t, y), dtype=float)
+        r1 = np.asarray(f1(t, y), dtype=float)
+        R0, R1 = r0.reshape((-1, V, N)), r1.reshape((-1, V, N))
+        R0[:, S, :] += (R1[:, S, :] - R0[:, S, :])*delta
+        return r0
+    return f, (p0,)
+
+
+def _g18_input(case):
+    kw = {"period": case["period"]} if "period" in case else {}
+    if "process-type" in case:
+        kw["process_type"] = case["process-type"]
+    return INP.ALL_N2_INPUTS[case["input"]](**kw)
+
+
+def _g18_bed(case, pr):
+    N = case["zNo"]
+    spec = case.get("axial-profile") or {}
+    a = g18_nodes(spec["position"], spec["catalyst-activity"], N) if "catalyst-activity" in spec else np.ones(N)
+    d = g18_nodes(spec["position"], spec["medium-temperature"], N) - pr["Tm"] if "medium-temperature" in spec else np.zeros(N)
+    return a, d
+
+
+def g18_trajectory(case, rtol=1e-10, atol=1e-13):
+    """Whole states at the output times (the G13 recipe on the profiled RHS; a "schedule" moves the common coolant level)"""
+    from oracle import n2_oracle as O
+    pr = dict(O.setup_n2(_g18_input(case), zNo=case["zNo"]))
+    a, d = _g18_bed(case, pr)
+    f, moved = g18_profiled_rhs(O, pr, a, d)
+    sch = case.get("schedule")
+    out_t = np.linspace(0.0, case["period"], case["tNo"] + 1)
+    marks = sorted(set(out_t.tolist()) | ({b for b in sch["time"] if 0 < b < case["period"]
+                                           and np.min(np.abs(out_t - b)) > 1e-12*case["period"]} if sch else set()))
+    y = np.array(pr["IV"], dtype=float)
+    states, nfev = [], 0
+    for lo, hi in zip(marks[:-1], marks[1:]):
+        piece = _pw_piece(sch["time"], np.asarray(sch["medium-temperature"], dtype=float), lo, hi) if sch else None
+
+        def ft(t, yy, piece=piece, lo=lo):
+            if piece is not None:
+                for p in moved:
+                    p["Tm"] = piece[0] + piece[1]*(t - lo)
+            return f(t, yy)
+        t0 = time.time()
+        sol = REAL_SOLVE_IVP(ft, (lo, hi), y, method=case.get("method", "LSODA"), rtol=rtol, atol=atol)
+        if not sol.success:
+            raise RuntimeError(sol.message)
+        y = sol.y[:, -1]
+        nfev += sol.nfev
+        print("G18 %s: (%.4f, %.4f) nfev=%d %.0f s" % (case.get("name", ""), lo, hi, sol.nfev, time.time() - t0), flush=True)
+        if np.min(np.abs(out_t - hi)) <= 1e-12*case["period"]:
+            states.append(y.copy())
+    return out_t[1:], np.array(states), nfev
+
+
+def g18_steady(case, rtol=1e-10, atol=1e-13):
+    """the recipe of g17_state on the profiled RHS"""
+    import scipy.optimize
+    from oracle import n2_oracle as O
+    pr = dict(O.setup_n2(_g18_input(case), zNo=case["zNo"]))
+    a, d = _g18_bed(case, pr)
+    f, _ = g18_profiled_rhs(O, pr, a, d)
+    y, t, prev = np.array(pr["IV"], dtype=float), 0.0, np.inf
+    while t < G17_T_MAX:
+        t0 = time.time()
+        sol = REAL_SOLVE_IVP(f, (t, t + G17_CHUNK), y, method="LSODA", rtol=rtol, atol=atol)
+        if not sol.success:
+            raise RuntimeError(sol.message)
+        y, t = sol.y[:, -1], t + G17_CHUNK
+        r = float(np.max(np.abs(f(t, y))))
+        print("G18 S: t = %.0f s max|f| = %.3e nfev=%d %.0f s" % (t, r, sol.nfev, time.time() - t0), flush=True)
+        if not r < 0.5*prev:
+            break
+        prev = r
+    r_ode = float(np.max(np.abs(f(t, y))))
+    best, r_best = y, r_ode
+    sol = scipy.optimize.root(lambda v: f(0.0, v), y)
+    r = float(np.max(np.abs(f(0.0, sol.x))))
+    print("G18 S: root max|f| = %.3e" % r, flush=True)
+    if np.all(np.isfinite(sol.x)) and r < r_best:
+        best, r_best = np.array(sol.x, dtype=float), r
+    return best, r_best, t, r_ode
+
+
+def g_profile(which=None):
+    path = os.path.join(GOLD, "g18_profile.json")
+    meta = {"cases": G18_CASES, "rtol": 1e-10, "atol": 1e-13, "gate": G17_GATE, "steady": {},
+            "reference": "SciPy LSODA (cases C, C0: DOP853) on oracle.n2_oracle.make_rhs_vec with the rates wrapped by the "
+                         "node activities and the coolant offsets through the affine dependence on Tm; case S: the recipe "
+                         "of G17"}
+    if os.path.exists(path):
+        with open(path) as fh:
+            meta["steady"] = json.load(fh).get("steady", {})
+    for name in ([which] if which else list(G18_CASES)):
+        case = dict(G18_CASES[name], name=name)
+        t0 = time.time()
+        if case.get("steady"):
+            y, r, t, r_ode = g18_steady(case)
+            if not r <= G17_GATE:
+                raise SystemExit("G18 S: max|f| = %.3e exceeds the gate %.1e - not written" % (r, G17_GATE))
+            np.savez_compressed(os.path.join(GOLD, "g18_profile_%s.npz" % name), state=y, residual=r)
+            meta["steady"] = {"residual": r, "time": t, "residual_lsoda": r_ode}
+        else:
+            times, states, nfev = g18_trajectory(case)
+            np.savez_compressed(os.path.join(GOLD, "g18_profile_%s.npz" % name), times=times, nfev=nfev,
+                                wall_s=time.time() - t0, states=states)
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+        print("G18 %s written (%.0f s)" % (name, time.time() - t0), flush=True)
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1307,6 +1476,8 @@ def main(argv):
             g_control(what.split("=", 1)[1] if "=" in what else None)
         elif what == "steady" or what.startswith("steady="):
             g_steady_state(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "profile" or what.startswith("profile="):
+            g_profile(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

@@ -207,6 +207,28 @@ int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* out, int nout
  * rejected = the number of nodes that needed a rejected step.  A member whose march fails (a node at max_iter, a
  * non-finite state, a zero pivot) gets RMT_N2_FLAG_STEP / RMT_N2_FLAG_NONFINITE and keeps the input downstream of it. */
 int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, int64_t max_iter, rmt_n2_stats* stats_out);
+/* Time-on-stream campaigns (solver-config "deactivation", csrc/kernels/72_campaign.inc): the bed is quasi-steady, its
+ * catalyst activity a_n follows da_n/dt = -k_d(T_n) (a_n - a_inf)^m, k_d(T) = k_ref exp(-(Ed/R)(1/T - 1/Tref)), T_n the
+ * node's temperature in kelvin (the member's inlet temperature in an iso-thermal run).  The three calls need a handle whose
+ * code object holds rmt_n2_campaign_step (generated with RMT_CAMPAIGN, RMT_WITH_MARCH and RMT_PROFILE; plan.profiled = 1)
+ * and whose profile table has been set (rmt_n2_set_profile: the fresh bed's activities and the coolant offsets); the
+ * second and third also a law.  Otherwise they return an error and rmt_n2_last_error names the function.
+ *  rmt_n2_set_campaign_law   law_host HOST [E][5] doubles {k_ref [1/s] > 0, Ed [J/mol] >= 0, Tref [K] > 0, m >= 1,
+ *                            0 <= a_inf < 1} per member; one blocking upload.
+ *  rmt_n2_campaign_step      ONE march of every member with the activities as they are in the handle's table (the kernel
+ *                            shape and the node solver of rmt_n2_steady_march, every node started from its converged
+ *                            upstream state), and at every converged node a_n <- the law's exact solution over `dt`
+ *                            seconds at that node's temperature, in place in the table.  dt = 0 changes no a_n (bit for bit).
+ *                            y DEVICE double [E][V][N] receives the marched state; log_row DEVICE [E][V+6] doubles = {the
+ *                            outlet state [V], peak theta, its node, mean and minimum of the activities the march read,
+ *                            worst scaled node residual, largest per-node step count}; stats as rmt_n2_steady_march, and so
+ *                            are a failed member's flags - it keeps its activities from the failed node on.  Enqueues ONE
+ *                            kernel on the handle's stream and synchronises nothing.
+ *  rmt_n2_get_profile        the handle's table as it is now into HOST [E][2][N] doubles; synchronises the stream. */
+int rmt_n2_set_campaign_law(rmt_n2_handle* h, const double* law_host);
+int rmt_n2_campaign_step(rmt_n2_handle* h, void* y, double dt, double tol, int64_t max_iter, double* log_row,
+                         rmt_n2_stats* stats_out);
+int rmt_n2_get_profile(rmt_n2_handle* h, double* table_host);
 /* copies the E flag words to host memory (synchronises the stream) and clears them on device */
 int rmt_n2_status(rmt_n2_handle* h, uint32_t* flags_host);
 /* which stepper rmt_n2_rk4 / rk45 / ros4 use: 0 = auto (on-chip if N fits one workgroup, else chained

@@ -8,6 +8,7 @@
 
 #include <dlfcn.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -60,7 +61,7 @@ struct rmt_n2_handle {
     hipFunction_t f_rhs = nullptr, f_rk4_reg = nullptr, f_rk4_mem = nullptr, f_rk45_reg = nullptr,
                   f_rk45_mem = nullptr, f_multistep = nullptr, f_rk4_chain = nullptr, f_ros4 = nullptr, f_n1 = nullptr,
                   f_ros4_chain = nullptr, f_rk45_chain = nullptr, f_rk4_redo = nullptr, f_rk4_chain_redo = nullptr,
-                  f_march = nullptr;
+                  f_march = nullptr, f_campaign = nullptr;
     unsigned long long* d_rings = nullptr;   // tagged-word links of the chained stiff stepper: rings, decision slots, abort words
     size_t ring_bytes = 0;
     double* d_members1 = nullptr;
@@ -92,6 +93,7 @@ struct rmt_n2_handle {
     int profiled = 0;
     double* d_profile = nullptr;
     hipDeviceptr_t profile_slot = nullptr;   // address of the module's `rmt_profile_tab`
+    double* d_law = nullptr;                 // campaign units (RMT_CAMPAIGN): the deactivation law rows [E][5]
 };
 
 // a profiled handle launches nothing before its table is there (the kernels would read through a null pointer)
@@ -263,6 +265,7 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
         {"rmt_n1_ros4", &rmt_n2_handle::f_n1, false},
         {"rmt_n2_ros4_chain", &rmt_n2_handle::f_ros4_chain, false},
         {"rmt_n2_steady_march", &rmt_n2_handle::f_march, false},
+        {"rmt_n2_campaign_step", &rmt_n2_handle::f_campaign, false},
     };
     for (const auto& k : kernels) {
         const hipError_t e = hipModuleGetFunction(&(h->*k.f), h->module, k.name);
@@ -309,6 +312,7 @@ extern "C" void rmt_n2_destroy(rmt_n2_handle* h) {
     if (h->fb_pending && h->ev_fb) (void)hipEventSynchronize(h->ev_fb);       // the counter copy into fb_host has landed
     if (h->d_members) (void)hipFree(h->d_members);
     if (h->d_profile) (void)hipFree(h->d_profile);
+    if (h->d_law) (void)hipFree(h->d_law);
     if (h->d_flags) (void)hipFree(h->d_flags);
     if (h->d_work) (void)hipFree(h->d_work);
     if (h->d_backup) (void)hipFree(h->d_backup);
@@ -773,6 +777,73 @@ extern "C" int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, in
     HIP_OK(hipModuleLaunchKernel(h->f_march, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
     HIP_OK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- campaign
+// solver-config "deactivation" (kernels/72_campaign.inc).  Each of the three entry points needs a code object with
+// rmt_n2_campaign_step, a profile table (rmt_n2_set_profile) and a law (rmt_n2_set_campaign_law); the first one sets the law
+// and therefore checks only what comes before it.
+#define RMT_N2_CAMPAIGN_LAW 5
+static int campaign_ready(const rmt_n2_handle* h, const char* who, bool need_law) {
+    if (!h->f_campaign)
+        return fail("%s: this handle's code object has no rmt_n2_campaign_step (generate it with RMT_CAMPAIGN, "
+                    "RMT_WITH_MARCH and RMT_PROFILE)", who);
+    if (!h->profiled || !h->d_profile) return fail("%s: no profile table has been set (rmt_n2_set_profile comes first)", who);
+    if (need_law && !h->d_law) return fail("%s: no deactivation law has been set (rmt_n2_set_campaign_law comes first)", who);
+    return 0;
+}
+
+extern "C" int rmt_n2_set_campaign_law(rmt_n2_handle* h, const double* law_host) {
+    if (!h || !law_host) return fail("rmt_n2_set_campaign_law: null argument");
+    if (campaign_ready(h, "rmt_n2_set_campaign_law", false)) return 1;
+    for (int e = 0; e < h->E; ++e) {
+        const double* l = law_host + (size_t)e * RMT_N2_CAMPAIGN_LAW;
+        if (!(l[0] > 0) || !(l[1] >= 0) || !(l[2] > 0) || !(l[3] >= 1) || !(l[4] >= 0 && l[4] < 1) || std::isinf(l[0]) ||
+            std::isinf(l[1]) || std::isinf(l[2]) || std::isinf(l[3]))
+            return fail("rmt_n2_set_campaign_law: member %d: need k_ref > 0, Ed >= 0, Tref > 0, m >= 1, 0 <= a_inf < 1, all "
+                        "finite", e);
+    }
+    ON_DEVICE(h);
+    const size_t bytes = (size_t)h->E * RMT_N2_CAMPAIGN_LAW * sizeof(double);
+    HIP_OK(hipStreamSynchronize(h->stream));          // (a step in flight may still read the old rows)
+    double* buf = h->d_law;
+    if (!buf) HIP_OK(hipMalloc((void**)&buf, bytes));
+    const hipError_t e = hipMemcpy(buf, law_host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (!h->d_law) (void)hipFree(buf);
+        return fail("rmt_n2_set_campaign_law: %s", hipGetErrorString(e));
+    }
+    h->d_law = buf;
+    return 0;
+}
+
+extern "C" int rmt_n2_campaign_step(rmt_n2_handle* h, void* y, double dt, double tol, int64_t max_iter, double* log_row,
+                                    rmt_n2_stats* stats) {
+    if (!h || !y || !log_row || !stats) return fail("rmt_n2_campaign_step: null argument");
+    if (campaign_ready(h, "rmt_n2_campaign_step", true)) return 1;
+    if (!(tol > 0) || max_iter < 1 || !(dt >= 0) || std::isinf(dt))
+        return fail("rmt_n2_campaign_step: bad arguments (dt >= 0 and finite, tolerance > 0, max_iter >= 1)");
+    if (h->fp32) return fail("rmt_n2_campaign_step: fp64 only");
+    ON_DEVICE(h);
+    int N = h->N, E = h->E;
+    long long mi = (long long)max_iter;
+    void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
+                    (void*)&h->d_flags, (void*)&h->d_profile, (void*)&h->d_law, (void*)&dt, (void*)&log_row};
+    HIP_OK(hipEventRecord(h->ev0, h->stream));
+    HIP_OK(hipModuleLaunchKernel(h->f_campaign, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    HIP_OK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return 0;
+}
+
+extern "C" int rmt_n2_get_profile(rmt_n2_handle* h, double* table_host) {
+    if (!h || !table_host) return fail("rmt_n2_get_profile: null argument");
+    if (campaign_ready(h, "rmt_n2_get_profile", true)) return 1;
+    ON_DEVICE(h);
+    HIP_OK(hipMemcpyAsync(table_host, h->d_profile, (size_t)h->E * 2 * (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost,
+                          h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
 

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from . import control, hipbind, initial, launches, monitor, plan, profile, schedule
+from . import campaign, control, hipbind, initial, launches, monitor, plan, profile, schedule
 from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
@@ -320,6 +320,20 @@ def march_plan(mech, N, defines=None, rows=None):
     if is_profiled(defines):          # (the march reads the table for the node it is solving)
         defs[profile.DEFINE] = "1"
     return code_plan(mech, N, False, None, MARCH_BLOCK, 1, None, defs, ("march",), rows, specialize=False)
+
+
+def is_campaign(defines):
+    """True for the prelude defines of the campaign unit (csrc/kernels/72_campaign.inc): the one unit generated from the
+    whole template text (plan.Mechanism.source cuts that file's text out of every other unit)."""
+    return str((defines or {}).get(campaign.DEFINE, "0")) == "1"
+
+
+def campaign_plan(mech, N, rows=None):
+    """The code object of a time-on-stream run (solver-config "deactivation", csrc/kernels/72_campaign.inc): the profiled
+    march unit (march_plan) plus RMT_CAMPAIGN - rmt_n2_campaign_step beside rmt_n2_steady_march.  The only unit such a run
+    loads; one object serves every operating point, law and mesh of a mechanism."""
+    cp = march_plan(mech, N, {profile.DEFINE: "1"}, rows)
+    return CodePlan(cp.block, cp.npt, cp.lds_state, {**cp.defines, campaign.DEFINE: "1"}, cp.features)
 
 
 def code_plans(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),
@@ -675,6 +689,37 @@ class N2Device:
         its, damped = step_counts(raw)
         return ({"scaled-residual": raw[:, 0].copy(), "failed-node": raw[:, 1].astype(np.int64), "iterations": its,
                  "nodes-damped": damped}, self.status())
+
+    def set_campaign_law(self, law):
+        """Upload the deactivation law [E][5] = {k_ref, Ed, Tref, m, a_inf} (rmt_n2_set_campaign_law: one blocking copy).
+        Needs the campaign unit (campaign_plan) and a profile table."""
+        law = np.ascontiguousarray(law, dtype=np.float64)
+        if law.shape != (self.E, len(campaign.LAW_KEYS)):
+            raise hipbind.RmtN2Error("the law must be [E][5] = %r doubles (got %r)" % ((self.E, 5), law.shape))
+        hipbind.check(hipbind.lib().rmt_n2_set_campaign_law(self.h, law.ctypes.data_as(C.POINTER(C.c_double))))
+        self.law = law
+
+    def campaign_step(self, y, dt, log_row, stats=None, tol=initial.DEFAULTS["tolerance"],
+                      max_iter=initial.DEFAULTS["max-iterations"]):
+        """One step of a campaign (rmt_n2_campaign_step): y becomes every member's steady state for the activities in the
+        handle's table, which then move over ``dt`` seconds at the node temperatures of that state.  ``log_row``: device
+        doubles [E][V+6]; ``stats``: device doubles [E][4] (default: the device's own, march_result reads them).  Queued on
+        the stream, nothing is synchronised."""
+        self._chk_state(y)
+        stats = self._stats if stats is None else stats
+        for t, n in ((log_row, self.E*(self.mech.V + campaign.LOG_EXTRA)), (stats, self.E*4)):
+            assert t.is_cuda and t.dtype == self.torch.float64 and t.is_contiguous() and t.numel() == n, \
+                "campaign_step: the log row is [E][V+6], the stats [E][4] device doubles"
+        hipbind.check(hipbind.lib().rmt_n2_campaign_step(self.h, C.c_void_p(y.data_ptr()), float(dt), float(tol),
+                                                         int(max_iter), C.c_void_p(log_row.data_ptr()),
+                                                         C.c_void_p(stats.data_ptr())))
+
+    def get_profile(self):
+        """The handle's table [E][2][N] as it is now (rmt_n2_get_profile; synchronises the stream): the activities the
+        campaign steps have written, and the coolant offsets."""
+        out = np.zeros((self.E, 2, self.N))
+        hipbind.check(hipbind.lib().rmt_n2_get_profile(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     def n1_profile(self, rows1, nout, rtol, atol, h0, max_steps, V1=None):
         """Steady-state model N1 (needs features=("n1",)): one profile per member row of ``rows1`` (layout M1_*),
@@ -1386,6 +1431,81 @@ def start_steady(dev, y, ini, mech):
     return [ini.result_entry(res[e], st["iterations"][e], st["nodes-damped"][e]) for e in range(E)]
 
 
+def run_campaign(modelInput, members_inputs, cam, pack_all, result):
+    """solver-config "deactivation" (campaign.py): the time-on-stream run of a quasi-steady bed.  Opens the members' rows
+    with the campaign unit only (campaign_plan), uploads the fresh bed's table and the law, and queues one launch of
+    rmt_n2_campaign_step per step (K + 1 launches; the log [K+1][E][V+6] and the march statistics [K+1][E][4] stay on the
+    device and come back once).  At every output step the activities a(t_k) (before the launch), the state and the status
+    words come to the host: a member whose march failed raises there through flag_error - the message names the member, the
+    node, the step and its time on stream - and not behind launches queued after the failed one."""
+    start = timer()
+    cfg = modelInput['solver-config']
+    zNo = int(cfg.get('zNo', solverSetting['N2']['zNo']))
+    inputs = list(members_inputs) if members_inputs else [modelInput]
+    mech = mechanism_for(modelInput, inputs, cfg)
+    cam.check_budget(mech.V, PIPELINE_BYTES)
+    prof = profile.parse(modelInput, members_inputs, None, False)
+    pairs = [plan.member_constants(mi, mech, zNo) for mi in inputs]
+    named, rows = [nm for nm, _ in pairs], np.array([r for _, r in pairs])
+    E = len(inputs)
+    table = prof.table() if prof is not None else np.stack([np.ones((E, zNo)), np.zeros((E, zNo))], axis=1)
+    IV = plan.initial_states(named, mech, zNo, plan.initial_state)
+    cp = campaign_plan(mech, zNo, rows)
+    dev = device_cls()(mech, rows, zNo, block=cp.block, npt=cp.npt, defines=cp.defines, specialize=False,
+                       features=cp.features, profile=table)
+    try:
+        import torch
+        dev.set_campaign_law(cam.law)
+        y = dev.to_device(IV)
+        log = torch.zeros((cam.K + 1, E, mech.V + campaign.LOG_EXTRA), dtype=torch.float64, device=y.device)
+        stats = torch.zeros((cam.K + 1, E, 4), dtype=torch.float64, device=y.device)
+        marks = {int(k): i for i, k in enumerate(cam.output_steps)}
+        acts, packs, checked = [table[:, 0].copy()], [[] for _ in named], 0
+        for k, dt in enumerate(cam.dts()):
+            if k in marks:
+                acts.append(dev.get_profile()[:, 0] if k else table[:, 0].copy())       # a(t_k): launch k moves it on
+            dev.campaign_step(y, dt, log[k], stats[k], cam.tolerance, cam.max_iterations)
+            if k not in marks:
+                continue
+            Yh = y.cpu().numpy()
+            flags = dev.status()
+            err = flag_error(flags)
+            if err is not None:
+                e = int(np.nonzero(flags)[0][0])
+                st = stats[checked:k + 1, e].cpu().numpy()
+                bad = np.nonzero(st[:, 1] >= 0)[0]
+                j = int(bad[0]) if len(bad) else len(st) - 1
+                raise type(err)("solver-config 'deactivation': the march failed at node %d of member %d in step %d (time "
+                                "on stream %g s; %d pseudo-time steps, 'max-iterations' = %d): %s"
+                                % (int(st[j, 1]), e, checked + j, cam.times[checked + j],
+                                   int(step_counts(st[j:j + 1])[0][0]), cam.max_iterations, err))
+            checked = k + 1
+            for e, pk in enumerate(pack_all(Yh, named, mech, zNo, float(cam.times[k]))):
+                packs[e].append(pk)
+        logs = log.cpu().numpy()
+        raw = stats.cpu().numpy()
+        dstats = {"launches": cam.K + 1, "steps": cam.K, "march-iterations": int(step_counts(raw.reshape(-1, 4))[0].max()),
+                  "nodes-damped": int(step_counts(raw.reshape(-1, 4))[1].sum())}
+    finally:
+        dev.close()
+    acts = np.array(acts)                                                   # [n_out+1][E][N]
+    entries = [campaign.result_entry(cam, e, logs[:, e], acts[:, e], mech, zNo, named[e]) for e in range(E)]
+    res = result(packs[0], modelInput, zNo, cam.outputs)
+    res["computation-time"] = np.round(timer() - start, ROUND_FUN_ACCURACY)
+    res["device-stats"] = dstats
+    if members_inputs:
+        res["ensemble"] = [result(p, mi, zNo, cam.outputs) for p, mi in zip(packs, inputs)]
+    res[campaign.KEY] = entries[0]
+    if prof is not None:
+        res["axial-profile"] = profile.result_entry(prof, 0)
+    if members_inputs:
+        for e, entry in enumerate(res["ensemble"]):
+            entry[campaign.KEY] = entries[e]
+            if prof is not None:
+                entry["axial-profile"] = profile.result_entry(prof, e)
+    return res
+
+
 def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result, fp32=False, defines=None,
                 with_schedule=False, outlet=False, display=False):
     """What run_n2 and m2.run_m2 share: the ranks of a torchrun job, the geometry of the `ivp`, the device(s), the walk
@@ -1550,6 +1670,14 @@ def run_n2(modelInput, members_inputs=None):
         if len(named) == 1 and not outlet:
             return [pack_interval(Yg[0], named[0], mech, zNo, t1, modelId)]
         return pack_intervals(Yg, named, mech, zNo, t1, modelId)
+    # "deactivation": a time-on-stream run of the quasi-steady bed (campaign.py) - no integration in time; absent = None =
+    # exactly the run without it
+    cam = campaign.parse(modelInput, members_inputs, active_ranks(len(members_inputs)) is not None if members_inputs else False)
+    if cam is not None:
+        if outlet:
+            raise ValueError("solver-config 'deactivation' cannot be combined with 'ensemble-output': 'outlet' - the "
+                             "campaign returns whole states (the outlet per step is in resModel['deactivation'])")
+        return run_campaign(modelInput, members_inputs, cam, pack_all, lambda dataPack, mi, zNo, opTSpan: {"dataPack": dataPack})
     return run_dynamic(modelInput, members_inputs, "N2", plan.member_constants, plan.initial_state, pack_all,
                        lambda dataPack, mi, zNo, opTSpan: {"dataPack": dataPack},
                        fp32=cfg.get('dtype', 'fp64') in ('fp32', 'float32'),

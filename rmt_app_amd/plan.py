@@ -298,9 +298,13 @@ class Mechanism:
         return need is not None and need <= 159*1024
 
     def source(self, template, fp32=False, block=1024, npt=1, lds_state=None, defines=None):
-        """Complete translation unit: prelude + template with the lowered kinetics spliced in."""
+        """Complete translation unit: prelude + template with the lowered kinetics spliced in.  The text of the campaign
+        step (csrc/kernels/72_campaign.inc, between its two marks) goes into the campaign unit only (RMT_CAMPAIGN): every
+        other unit's source, and with it its cache key, is what it is without that file."""
         if "RMT_KINETICS_SOURCE" not in template:
             raise ValueError("kernel template lacks the RMT_KINETICS_SOURCE marker")
+        if str((defines or {}).get("RMT_CAMPAIGN", "0")) != "1":
+            template = without_campaign(template)
         # one reciprocal for the independent divisions of the rate laws (lowering.Lowered.div_groups).  RMT_DIV_BATCH is
         # a switch of this generator, not a macro the kernel source reads: 0 switches the pass off.  Not in a unit that
         # also prints the gradient DAG (the same two conditions as below): the stiff and the steady steppers take the
@@ -381,6 +385,18 @@ class Mechanism:
         h = hashlib.sha256()
         h.update(self.source(template, fp32, block, npt, lds_state, defines).encode())
         return h.hexdigest()[:24]
+
+
+CAMPAIGN_MARKS = ("//>>> RMT_CAMPAIGN", "//<<< RMT_CAMPAIGN\n")
+
+
+def without_campaign(template):
+    """The device template without the text of csrc/kernels/72_campaign.inc (from its opening mark to the end of its
+    closing one); a template that has no such text comes back as it is."""
+    lo, hi = template.find(CAMPAIGN_MARKS[0]), template.find(CAMPAIGN_MARKS[1])
+    if lo < 0 or hi < lo:
+        return template
+    return template[:lo] + template[hi + len(CAMPAIGN_MARKS[1]):]
 
 
 GAMACOTE_N2_ERROR = "setting an array element with a sequence."

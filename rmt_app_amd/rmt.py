@@ -38,6 +38,8 @@ def rmtExe(modelInput):
         check_initial(modelInput)             # solver-config 'initial': model N2 only
         from .profile import check_model as check_profile
         check_profile(modelInput)             # solver-config 'axial-profile': model N2 only
+        from .campaign import check_model as check_campaign
+        check_campaign(modelInput)            # solver-config 'deactivation': model N2 only
         if modelType == "N2":
             from .n2 import run_n2
             ensemble = modelInput['solver-config'].get('ensemble')

@@ -5,11 +5,12 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
 coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
 closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|syn12]: discrete steady states of model N2,
-G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18 - like G13..G15 these
+G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18; campaign[=DA|DB|DC|DI]:
+time-on-stream runs with catalyst deactivation, G19 - like G13..G15 these
 run SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
@@ -1441,6 +1442,38 @@ def g_profile(which=None):
         print("G18 %s written (%.0f s)" % (name, time.time() - t0), flush=True)
 
 
+# ------------------------------------------------------------------ G19: time-on-stream runs with catalyst deactivation
+# (solver-config "deactivation", rmt_app_amd/campaign.py).  The oracle does not change and nothing of the product is
+# imported: tests/campaign_ref.py restates the law in numpy and finds every steady state with scipy.optimize.root on the
+# profiled right-hand side of G18, started from the previous step's state (above the gate of G17: LSODA legs first).
+def g_campaign(which=None):
+    import campaign_ref as CR
+    from oracle import n2_oracle as O
+    path = os.path.join(GOLD, "g19_campaign.json")
+    meta = {"cases": {}, "gate": CR.GATE,
+            "reference": "per step scipy.optimize.root on profile_ref.profiled_rhs from the previous step's state (above the "
+                         "gate: the recipe of G17 - LSODA legs from the cold start until max|f| stops falling, then root), the activity moved by the frozen-temperature "
+                         "exact solution of the law in numpy (tests/campaign_ref.py)"}
+    if os.path.exists(path):
+        with open(path) as fh:
+            meta["cases"] = json.load(fh)["cases"]
+    for name in ([which] if which else list(CR.CASES)):
+        case = CR.CASES[name]
+        t0 = time.time()
+        out = CR.run_case(O, INP, case, log=lambda msg: print("G19 %s: %s" % (name, msg), flush=True))
+        np.savez_compressed(os.path.join(GOLD, "g19_campaign_%s.npz" % name), times=out["times"], marks=out["marks"],
+                            activity=out["activity"], states=out["states"], residual=out["residual"], delta=out["delta"])
+        if os.path.exists(path):
+            with open(path) as fh:
+                meta["cases"] = json.load(fh)["cases"]
+        meta["cases"][name] = dict(case, residual=float(out["residual"].max()), lsoda_steps=int(np.sum(out["legs"] > 0)),
+                                   activity_end=[float(out["activity"][-1].min()), float(out["activity"][-1].max())])
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+        print("G19 %s written (%.0f s): max|f| <= %.3e, activity ends at %.4f .. %.4f" % (
+            name, time.time() - t0, out["residual"].max(), out["activity"][-1].min(), out["activity"][-1].max()), flush=True)
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1478,6 +1511,8 @@ def main(argv):
             g_steady_state(what.split("=", 1)[1] if "=" in what else None)
         elif what == "profile" or what.startswith("profile="):
             g_profile(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "campaign" or what.startswith("campaign="):
+            g_campaign(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

@@ -229,6 +229,34 @@ int rmt_n2_set_campaign_law(rmt_n2_handle* h, const double* law_host);
 int rmt_n2_campaign_step(rmt_n2_handle* h, void* y, double dt, double tol, int64_t max_iter, double* log_row,
                          rmt_n2_stats* stats_out);
 int rmt_n2_get_profile(rmt_n2_handle* h, double* table_host);
+/* Constant-yield operation of a campaign (solver-config "deactivation" "policy", csrc/kernels/72_campaign.inc under
+ * RMT_CAMPAIGN_POLICY): per member and step the common coolant level T [K] (the member field TM; the zones of the profile
+ * table keep their offsets) is moved within [lo, hi] so that the outlet mole fraction of one component equals a target -
+ * a bracketing root-find (the limits, the carried level, Illinois regula falsi) in which every function value is a whole
+ * march, all inside ONE kernel, one reactor per lane.  The three calls need what the campaign's calls need - the table and
+ * the law - and a code object that also holds rmt_n2_campaign_policy_step (generated with RMT_CAMPAIGN_POLICY beside
+ * RMT_CAMPAIGN); the second and third also the policy.  Otherwise they return an error naming the function.
+ *  rmt_n2_set_campaign_policy   rows_host HOST [E][4] doubles {target in (0, 1), lo, hi [K] with 0 < lo <= hi, tolerance > 0
+ *                               (absolute, on the mole fraction)}, `component` the index of the held species, levels_host
+ *                               HOST [E] the levels step 0 carries in (within the member's limits); one blocking upload.
+ *  rmt_n2_campaign_policy_step  as rmt_n2_campaign_step, with the root-find around the march: y, log_row and stats
+ *                               describe the march at the accepted level, which is always the last one marched, and the
+ *                               activities move over `dt` at the temperatures of that state.  policy_row DEVICE [E][4]
+ *                               doubles = {accepted level [K], held mole fraction, marches of this step, saturated: -1 at
+ *                               lo, 0 inside, +1 at hi}.  No sign change between the limits: the limit with the smaller
+ *                               |r| is accepted (a tie: lo).  A member whose bracket falls below 1e-9 K with |r| above
+ *                               the tolerance (the outlet jumps there: a node changed branch) gets
+ *                               RMT_N2_FLAG_POLICY_BRACKET and policy_row[3] = 2, one that reaches `max_evaluations`
+ *                               (>= 4) marches RMT_N2_FLAG_POLICY_EVALS and 3; like a member whose node solve fails in
+ *                               any march they keep their activities and their carried level.  ONE kernel, nothing is
+ *                               synchronised.
+ *  rmt_n2_get_campaign_level    the carried levels as they are now into HOST [E] doubles; synchronises the stream. */
+#define RMT_N2_FLAG_POLICY_BRACKET 64u
+#define RMT_N2_FLAG_POLICY_EVALS 128u
+int rmt_n2_set_campaign_policy(rmt_n2_handle* h, const double* rows_host, int component, const double* levels_host);
+int rmt_n2_campaign_policy_step(rmt_n2_handle* h, void* y, double dt, double tol, int64_t max_iter, int max_evaluations,
+                                double* log_row, double* policy_row, rmt_n2_stats* stats_out);
+int rmt_n2_get_campaign_level(rmt_n2_handle* h, double* levels_host);
 /* copies the E flag words to host memory (synchronises the stream) and clears them on device */
 int rmt_n2_status(rmt_n2_handle* h, uint32_t* flags_host);
 /* which stepper rmt_n2_rk4 / rk45 / ros4 use: 0 = auto (on-chip if N fits one workgroup, else chained

@@ -29,8 +29,29 @@
   'catalyst-activity' of an "axial-profile" at 'position'), per step "mean-activity", "min-activity", "outlet" (as
   monitor.result_entry: mole fractions and T in K, with "labelList"), "peak-temperature", "peak-position", "iterations"
   (the largest per-node count of that march), "residual" (its worst scaled node residual), and "law".
-* Not built: other laws (concentration-dependent poisoning, coking), operating policies over time on stream, adaptive
-  activity steps, a warm start from the previous step's state, models other than N2, fp32, multi-rank runs.
+* Constant-yield operation - the optional key "policy" inside "deactivation":
+      "policy": {"hold": "outlet-mole-fraction", "component": "DME", "target": 0.0150,      # target in (0, 1)
+                 "manipulated": "medium-temperature", "limits": [503.0, 543.0],             # K, 0 < lo <= hi
+                 "tolerance": 1e-10, "max-evaluations": 40}                                 # absolute, on x_c; marches per step >= 4
+  moves the common coolant level T (the member's MeTe; the zones of an "axial-profile" keep their offsets) in every step
+  so that r(T) = x_c,outlet(T) - target = 0, inside ONE launch of rmt_n2_campaign_policy_step (the policy unit,
+  n2.campaign_policy_plan; a run without the key loads the unit it always did and returns the same bits).  Every value of
+  r is a whole march.  The scheme, which `policy_emulate` below restates: march at lo and at hi; without a sign change
+  the limit with the smaller |r| is accepted (a tie: lo) and the step is "saturated"; else one march at the carried level
+  (step 0: MeTe clipped to the limits, then the previous step's accepted level) shrinks the bracket and Illinois regula
+  falsi runs until |r| <= "tolerance".  A bracket below 1e-9 K with |r| above the tolerance (the outlet jumps there: a node
+  changed its branch of steady states) and "max-evaluations" marches without convergence raise, naming the member, the
+  step and its time on stream.  The sign of dr/dT is taken from the bracket: the outlet of the DME bed is not monotone in
+  the coolant level over its life.  Where the bracket holds several roots the policy takes the one Illinois reaches from
+  the limits.  The accepted level is always the last one marched, so the state, the dataPack entries and the per-step
+  entries above are those of the accepted march; the activities move after it, at its temperatures.  It raises for an
+  iso-thermal run and for MeTe = 0 (the adiabatic switch).  A member of the list form may carry its own 'target' and
+  'limits'.  Result: resModel["deactivation"]["policy"] with, per step, "medium-temperature" [K], "held", "evaluations",
+  "saturated" (-1 at lo, 0 inside, +1 at hi), and "end-of-run": the time on stream of the first saturated step, or None.
+* Not built: other laws (concentration-dependent poisoning, coking), other held quantities (conversion, peak
+  temperature) and other manipulated ones (inlet temperature, pressure), tracking the previous root with a narrow
+  bracket, adaptive activity steps, a warm start from the previous step's state, models other than N2, fp32, multi-rank
+  runs.
 
 Host side only (numpy): parsing and validation, the step times, the law in numpy and the result entry.
 """
@@ -40,7 +61,19 @@ from . import initial
 
 KEY = "deactivation"
 LAW_KEYS = ("rate-constant", "activation-energy", "reference-temperature", "order", "residual-activity")
-KEYS = ("time-on-stream", "steps") + LAW_KEYS + ("tolerance", "max-iterations")
+KEYS = ("time-on-stream", "steps") + LAW_KEYS + ("tolerance", "max-iterations", "policy")
+POLICY = "policy"
+POLICY_KEYS = ("hold", "component", "target", "manipulated", "limits", "tolerance", "max-evaluations")
+POLICY_MEMBER_KEYS = ("target", "limits")            # what a member of the list form may carry of its own
+POLICY_DEFAULTS = {"tolerance": 1e-10, "max-evaluations": 40}
+POLICY_HOLD, POLICY_MANIPULATED = "outlet-mole-fraction", "medium-temperature"
+POLICY_DEFINE = "RMT_CAMPAIGN_POLICY"
+POLICY_ROW = 4           # csrc/kernels/72_campaign.inc RMT_POLICY_ROW: {target, lo, hi, tolerance}
+POLICY_LOG = 4           # ... RMT_POLICY_LOG: {level, held, marches, saturated}
+LEVEL, HELD, EVALUATIONS, SATURATED = range(POLICY_LOG)
+MIN_BRACKET = 1e-9       # ... RMT_POLICY_MIN_BRACKET, K
+FLAG_POLICY_BRACKET, FLAG_POLICY_EVALS = 64, 128     # include/rmt_n2.h RMT_N2_FLAG_POLICY_*
+BRACKET_COLLAPSED, EVALUATION_LIMIT = 2, 3           # `saturated` of a step that failed (device log and policy_emulate)
 EXCLUDES = ("schedule", "control", "monitor", "initial")
 MODELS = ("N2",)
 DEFINE = "RMT_CAMPAIGN"
@@ -92,7 +125,8 @@ class Campaign:
     ``times`` [K+1] (every step time, 0 first), ``output_steps`` [n_out] (indices into times), ``law`` [E][5] =
     {k_ref, Ed, Tref, m, a_inf}, ``tolerance``, ``max_iterations``."""
 
-    def __init__(self, outputs, steps, law, tolerance, max_iterations):
+    def __init__(self, outputs, steps, law, tolerance, max_iterations, policy=None):
+        self.policy = policy             # a Policy, or None: the coolant stays where the member rows have it
         self.outputs = np.asarray(outputs, dtype=np.float64)
         self.steps = int(steps)
         self.law = np.ascontiguousarray(law, dtype=np.float64).reshape(-1, len(LAW_KEYS))
@@ -114,8 +148,9 @@ class Campaign:
         return np.append(np.diff(self.times), 0.0)
 
     def check_budget(self, V, cap):
-        """The device log [K+1][E][V+6] doubles must not exceed ``cap`` bytes (n2.PIPELINE_BYTES)."""
-        need = (self.K + 1)*self.E*(int(V) + LOG_EXTRA)*8
+        """The device log [K+1][E][V+6] doubles (with a policy: and its [K+1][E][4]) must not exceed ``cap`` bytes
+        (n2.PIPELINE_BYTES)."""
+        need = (self.K + 1)*self.E*(int(V) + LOG_EXTRA + (POLICY_LOG if self.policy is not None else 0))*8
         if need > cap:
             raise ValueError("solver-config 'deactivation': %d output times x 'steps' = %d make %d launches of %d members "
                              "= %d bytes of log, more than the %d allowed - lower 'steps'"
@@ -173,8 +208,8 @@ def parse(modelInput, members_inputs=None, multi_rank=False):
         for k in own:
             if k not in KEYS:
                 raise ValueError("solver-config 'deactivation'%s: unknown key %r" % (who, k))
-            if k not in LAW_KEYS:
-                same = np.array_equal(np.asarray(own[k], dtype=object), np.asarray(spec[k], dtype=object)) \
+            if k not in LAW_KEYS and k != POLICY:           # (a member's "policy": _policy below)
+                same =np.array_equal(np.asarray(own[k], dtype=object), np.asarray(spec[k], dtype=object)) \
                     if k in spec else False
                 if not same:
                     raise ValueError("solver-config 'deactivation'%s: %r differs from the base input's - a member may "
@@ -185,7 +220,168 @@ def parse(modelInput, members_inputs=None, multi_rank=False):
                                   "is an fp64 kernel")
     if multi_rank:
         raise NotImplementedError("solver-config 'deactivation' is not available in a multi-rank run")
-    return Campaign(out, steps, law, tol, it)
+    return Campaign(out, steps, law, tol, it, _policy(modelInput, spec, inputs))
+
+
+class Policy:
+    """A parsed "policy" of E members: ``component`` (name) and ``index`` (into the feed's component list), ``rows`` [E][4] =
+    {target, lo, hi, tolerance} as the device takes them, ``levels`` [E] (the level step 0 carries in: the member's MeTe
+    clipped to its limits), ``tolerance``, ``max_evaluations``."""
+
+    def __init__(self, component, index, rows, levels, max_evaluations):
+        self.component, self.index = component, int(index)
+        self.rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, POLICY_ROW)
+        self.levels = np.ascontiguousarray(levels, dtype=np.float64)
+        self.tolerance = float(self.rows[0, 3])
+        self.max_evaluations = int(max_evaluations)
+
+
+def _policy_target_limits(pol, who):
+    def bad(key, what, v):
+        raise ValueError("solver-config 'deactivation' 'policy'%s: %r must be %s (got %r)" % (who, key, what, v))
+    for key in POLICY_MEMBER_KEYS:
+        if key not in pol:
+            raise ValueError("solver-config 'deactivation' 'policy'%s needs %r" % (who, key))
+    target = pol['target']
+    if not _number(target) or not 0 < target < 1:
+        bad('target', "a mole fraction in (0, 1)", target)
+    lim = pol['limits']
+    if not isinstance(lim, (list, tuple, np.ndarray)) or len(lim) != 2 or not all(_number(v) for v in lim) \
+            or not 0 < lim[0] <= lim[1]:
+        bad('limits', "[lo, hi] in kelvin with 0 < lo <= hi", lim)
+    return float(target), float(lim[0]), float(lim[1])
+
+
+def _policy(modelInput, spec, inputs):
+    """The Policy of a run (None without the key), or ValueError naming 'deactivation' 'policy' and the offending entry."""
+    pol = spec.get(POLICY)
+    for e, mi in enumerate(inputs):                  # (a member cannot bring a policy the base input has not)
+        own = (mi.get('solver-config') or {}).get(KEY) if mi is not modelInput else None
+        if pol is None and isinstance(own, dict) and own is not spec and own.get(POLICY) is not None:
+            raise ValueError("solver-config 'deactivation' of member %d: 'policy' differs from the base input's, which has "
+                             "none - a member may carry its own %s of the base input's policy" % (e, POLICY_MEMBER_KEYS))
+    if pol is None:
+        return None
+    if not isinstance(pol, dict):
+        raise ValueError("solver-config 'deactivation' 'policy' must be a dict with the keys %s" % (POLICY_KEYS,))
+    for k in pol:
+        if k not in POLICY_KEYS:
+            raise ValueError("solver-config 'deactivation' 'policy': unknown key %r (known: %s)" % (k, ", ".join(POLICY_KEYS)))
+    for key, only in (("hold", POLICY_HOLD), ("manipulated", POLICY_MANIPULATED)):
+        if pol.get(key) != only:
+            raise ValueError("solver-config 'deactivation' 'policy': %r must be %r (got %r) - other %s quantities are not "
+                             "built" % (key, only, pol.get(key), "held" if key == "hold" else "manipulated"))
+    comps = list(modelInput['feed']['components']['shell'])
+    comp = pol.get('component')
+    if comp not in comps:
+        raise ValueError("solver-config 'deactivation' 'policy': unknown 'component' %r (the feed has %s)"
+                         % (comp, ", ".join(comps)))
+    ptol = pol.get('tolerance', POLICY_DEFAULTS['tolerance'])
+    if not _number(ptol) or not ptol > 0:
+        raise ValueError("solver-config 'deactivation' 'policy': 'tolerance' must be a positive number (got %r)" % (ptol,))
+    mev = pol.get('max-evaluations', POLICY_DEFAULTS['max-evaluations'])
+    if isinstance(mev, (bool, np.bool_)) or not isinstance(mev, (int, np.integer)) or mev < 4:
+        raise ValueError("solver-config 'deactivation' 'policy': 'max-evaluations' must be an integer >= 4 (got %r)" % (mev,))
+    if modelInput['operating-conditions'].get('process-type') == "iso-thermal":
+        raise ValueError("solver-config 'deactivation' 'policy': 'manipulated' %r needs an energy balance - process-type "
+                         "'iso-thermal' has none" % (POLICY_MANIPULATED,))
+    base = _policy_target_limits(pol, "")
+    rows, levels = [], []
+    for e, mi in enumerate(inputs):
+        own = (mi.get('solver-config') or {}).get(KEY) if mi is not modelInput else None
+        own = own.get(POLICY) if isinstance(own, dict) and own is not spec else None
+        tl = base
+        if own is not None and own is not pol:
+            who = " of member %d" % e
+            if not isinstance(own, dict):
+                raise ValueError("solver-config 'deactivation' 'policy'%s must be a dict" % who)
+            for k in own:
+                if k not in POLICY_KEYS:
+                    raise ValueError("solver-config 'deactivation' 'policy'%s: unknown key %r" % (who, k))
+                if k not in POLICY_MEMBER_KEYS and (k not in pol or own[k] != pol[k]):
+                    raise ValueError("solver-config 'deactivation' 'policy'%s: %r differs from the base input's - a member "
+                                     "may carry its own %s only" % (who, k, " and ".join(POLICY_MEMBER_KEYS)))
+            tl = _policy_target_limits({**{k: pol[k] for k in POLICY_MEMBER_KEYS}, **own}, who)
+        mete = float(mi['external-heat']['MeTe'])
+        if mete == 0:
+            raise ValueError("solver-config 'deactivation' 'policy': 'manipulated' %r needs a member with external-heat MeTe "
+                             "> 0 (MeTe = 0 is the adiabatic switch); member %d has MeTe = 0" % (POLICY_MANIPULATED, e))
+        rows.append(tl + (float(ptol),))
+        levels.append(min(max(mete, tl[1]), tl[2]))
+    return Policy(comp, comps.index(comp), rows, levels, mev)
+
+
+def policy_emulate(row, carried, max_evaluations, r):
+    """One step of the policy's root-find in numpy, as rmt_n2_campaign_policy_step writes it.  ``row`` = (target, lo, hi,
+    tolerance), ``carried`` the level the step carries in, ``r``: a callable T -> x_c,outlet(T) - target (one march per
+    call), or a sequence of such values that is consumed in order.  Returns dict(levels: every level marched, in order;
+    level: the last one; residual: r there; evaluations; saturated: -1 | 0 | +1, or BRACKET_COLLAPSED / EVALUATION_LIMIT
+    for a step the device flags)."""
+    _, lo, hi, ptol = (float(v) for v in row)
+    carried = float(carried)
+    if not callable(r):
+        values = iter(r)
+        r = lambda T: next(values)
+    levels = []
+
+    def march(T):
+        levels.append(T)
+        return float(r(T))
+
+    def done(sat, res):
+        return {"levels": levels, "level": levels[-1], "residual": res, "evaluations": len(levels), "saturated": sat}
+    a, b = lo, hi
+    ra = march(lo)
+    if lo == hi:
+        return done(-1, ra)
+    rb = march(hi)
+    if not ra*rb < 0.0:
+        if abs(rb) < abs(ra):
+            return done(1, rb)
+        return done(-1, march(lo))                 # (the accepted level is the last one marched)
+    side = 0
+    if lo < carried < hi:
+        T, illinois = carried, False
+    else:
+        T = a - ra*(b - a)/(rb - ra)
+        T, illinois = (T if a < T < b else 0.5*(a + b)), True
+    while True:
+        res = march(T)
+        if abs(res) <= ptol:
+            return done(0, res)
+        if res*rb > 0.0:
+            b, rb = T, res
+            if illinois and side == 1:
+                ra *= 0.5
+            side = 1
+        else:
+            a, ra = T, res
+            if illinois and side == -1:
+                rb *= 0.5
+            side = -1
+        if not illinois:
+            side, illinois = 0, True
+        if b - a < MIN_BRACKET:
+            return done(BRACKET_COLLAPSED, res)
+        if len(levels) >= int(max_evaluations):
+            return done(EVALUATION_LIMIT, res)
+        T = a - ra*(b - a)/(rb - ra)
+        if not a < T < b:
+            T = 0.5*(a + b)
+
+
+def policy_entry(cam, e, plog):
+    """resModel["deactivation"]["policy"] of member e from its policy log rows [K+1][4]."""
+    plog = np.asarray(plog, dtype=np.float64).reshape(cam.K + 1, POLICY_LOG)
+    sat = plog[:, SATURATED].astype(np.int64)
+    hit = np.nonzero(sat != 0)[0]
+    pol = cam.policy
+    return {"hold": POLICY_HOLD, "component": pol.component, "manipulated": POLICY_MANIPULATED,
+            "target": float(pol.rows[e, 0]), "limits": [float(pol.rows[e, 1]), float(pol.rows[e, 2])],
+            "tolerance": pol.tolerance, "max-evaluations": pol.max_evaluations,
+            "medium-temperature": plog[:, LEVEL].copy(), "held": plog[:, HELD].copy(),
+            "evaluations": plog[:, EVALUATIONS].astype(np.int64), "saturated": sat,
+            "end-of-run": float(cam.times[hit[0]]) if len(hit) else None}
 
 
 def emulate(a, T, dt, law):

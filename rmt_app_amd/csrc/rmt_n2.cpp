@@ -61,7 +61,7 @@ struct rmt_n2_handle {
     hipFunction_t f_rhs = nullptr, f_rk4_reg = nullptr, f_rk4_mem = nullptr, f_rk45_reg = nullptr,
                   f_rk45_mem = nullptr, f_multistep = nullptr, f_rk4_chain = nullptr, f_ros4 = nullptr, f_n1 = nullptr,
                   f_ros4_chain = nullptr, f_rk45_chain = nullptr, f_rk4_redo = nullptr, f_rk4_chain_redo = nullptr,
-                  f_march = nullptr, f_campaign = nullptr;
+                  f_march = nullptr, f_campaign = nullptr, f_policy = nullptr;
     unsigned long long* d_rings = nullptr;   // tagged-word links of the chained stiff stepper: rings, decision slots, abort words
     size_t ring_bytes = 0;
     double* d_members1 = nullptr;
@@ -94,6 +94,10 @@ struct rmt_n2_handle {
     double* d_profile = nullptr;
     hipDeviceptr_t profile_slot = nullptr;   // address of the module's `rmt_profile_tab`
     double* d_law = nullptr;                 // campaign units (RMT_CAMPAIGN): the deactivation law rows [E][5]
+    // policy units (RMT_CAMPAIGN_POLICY): the rows [E][4] = {target, lo, hi, tolerance} with the carried coolant levels [E]
+    // behind them in ONE allocation, and the index of the held component
+    double* d_policy = nullptr;
+    int policy_comp = -1;
 };
 
 // a profiled handle launches nothing before its table is there (the kernels would read through a null pointer)
@@ -266,6 +270,7 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
         {"rmt_n2_ros4_chain", &rmt_n2_handle::f_ros4_chain, false},
         {"rmt_n2_steady_march", &rmt_n2_handle::f_march, false},
         {"rmt_n2_campaign_step", &rmt_n2_handle::f_campaign, false},
+        {"rmt_n2_campaign_policy_step", &rmt_n2_handle::f_policy, false},
     };
     for (const auto& k : kernels) {
         const hipError_t e = hipModuleGetFunction(&(h->*k.f), h->module, k.name);
@@ -313,6 +318,7 @@ extern "C" void rmt_n2_destroy(rmt_n2_handle* h) {
     if (h->d_members) (void)hipFree(h->d_members);
     if (h->d_profile) (void)hipFree(h->d_profile);
     if (h->d_law) (void)hipFree(h->d_law);
+    if (h->d_policy) (void)hipFree(h->d_policy);
     if (h->d_flags) (void)hipFree(h->d_flags);
     if (h->d_work) (void)hipFree(h->d_work);
     if (h->d_backup) (void)hipFree(h->d_backup);
@@ -843,6 +849,82 @@ extern "C" int rmt_n2_get_profile(rmt_n2_handle* h, double* table_host) {
     ON_DEVICE(h);
     HIP_OK(hipMemcpyAsync(table_host, h->d_profile, (size_t)h->E * 2 * (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost,
                           h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The coolant policy of a campaign (solver-config "deactivation" "policy", kernels/72_campaign.inc under
+// RMT_CAMPAIGN_POLICY).  Each of the three entry points needs what the campaign's need and a code object with
+// rmt_n2_campaign_policy_step; the second and third also the policy rows, which the first one sets.
+#define RMT_N2_POLICY_ROW 4
+static int policy_ready(const rmt_n2_handle* h, const char* who, bool need_policy) {
+    if (!h->f_policy)
+        return fail("%s: this handle's code object has no rmt_n2_campaign_policy_step (generate it with RMT_CAMPAIGN_POLICY "
+                    "beside RMT_CAMPAIGN, RMT_WITH_MARCH and RMT_PROFILE)", who);
+    if (campaign_ready(h, who, true)) return 1;
+    if (need_policy && !h->d_policy)
+        return fail("%s: no policy has been set (rmt_n2_set_campaign_policy comes first)", who);
+    return 0;
+}
+
+extern "C" int rmt_n2_set_campaign_policy(rmt_n2_handle* h, const double* rows_host, int component,
+                                          const double* levels_host) {
+    if (!h || !rows_host || !levels_host) return fail("rmt_n2_set_campaign_policy: null argument");
+    if (policy_ready(h, "rmt_n2_set_campaign_policy", false)) return 1;
+    if (component < 0 || component >= h->S)
+        return fail("rmt_n2_set_campaign_policy: bad arguments (component %d is not one of the %d species)", component, h->S);
+    for (int e = 0; e < h->E; ++e) {
+        const double* r = rows_host + (size_t)e * RMT_N2_POLICY_ROW;
+        const double l = levels_host[e];
+        if (!(r[0] > 0 && r[0] < 1) || !(r[1] > 0) || !(r[1] <= r[2]) || std::isinf(r[2]) || !(r[3] > 0) || std::isinf(r[3]) ||
+            !(l >= r[1] && l <= r[2]))
+            return fail("rmt_n2_set_campaign_policy: bad arguments (member %d: need 0 < target < 1, 0 < lo <= hi, tolerance > "
+                        "0, lo <= level <= hi, all finite)", e);
+    }
+    ON_DEVICE(h);
+    const size_t nrow = (size_t)h->E * RMT_N2_POLICY_ROW, bytes = (nrow + (size_t)h->E) * sizeof(double);
+    HIP_OK(hipStreamSynchronize(h->stream));          // (a step in flight may still read the old rows)
+    double* buf = h->d_policy;
+    if (!buf) HIP_OK(hipMalloc((void**)&buf, bytes));
+    hipError_t e = hipMemcpy(buf, rows_host, nrow * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + nrow, levels_host, (size_t)h->E * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (!h->d_policy) (void)hipFree(buf);
+        return fail("rmt_n2_set_campaign_policy: %s", hipGetErrorString(e));
+    }
+    h->d_policy = buf;
+    h->policy_comp = component;
+    return 0;
+}
+
+extern "C" int rmt_n2_campaign_policy_step(rmt_n2_handle* h, void* y, double dt, double tol, int64_t max_iter,
+                                           int max_evaluations, double* log_row, double* policy_row, rmt_n2_stats* stats) {
+    if (!h || !y || !log_row || !policy_row || !stats) return fail("rmt_n2_campaign_policy_step: null argument");
+    if (policy_ready(h, "rmt_n2_campaign_policy_step", true)) return 1;
+    if (!(tol > 0) || max_iter < 1 || !(dt >= 0) || std::isinf(dt) || max_evaluations < 4)
+        return fail("rmt_n2_campaign_policy_step: bad arguments (dt >= 0 and finite, tolerance > 0, max_iter >= 1, "
+                    "max_evaluations >= 4)");
+    if (h->fp32) return fail("rmt_n2_campaign_policy_step: fp64 only");
+    ON_DEVICE(h);
+    int N = h->N, E = h->E, comp = h->policy_comp;
+    long long mi = (long long)max_iter;
+    double* levels = h->d_policy + (size_t)E * RMT_N2_POLICY_ROW;
+    void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
+                    (void*)&h->d_flags, (void*)&h->d_profile, (void*)&h->d_law, (void*)&dt, (void*)&log_row,
+                    (void*)&h->d_policy, (void*)&levels, (void*)&policy_row, (void*)&comp, (void*)&max_evaluations};
+    HIP_OK(hipEventRecord(h->ev0, h->stream));
+    HIP_OK(hipModuleLaunchKernel(h->f_policy, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    HIP_OK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return 0;
+}
+
+extern "C" int rmt_n2_get_campaign_level(rmt_n2_handle* h, double* levels_host) {
+    if (!h || !levels_host) return fail("rmt_n2_get_campaign_level: null argument");
+    if (policy_ready(h, "rmt_n2_get_campaign_level", true)) return 1;
+    ON_DEVICE(h);
+    HIP_OK(hipMemcpyAsync(levels_host, h->d_policy + (size_t)h->E * RMT_N2_POLICY_ROW, (size_t)h->E * sizeof(double),
+                          hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }

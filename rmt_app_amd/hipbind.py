@@ -77,6 +77,9 @@ def lib():
     L.rmt_n2_set_campaign_law.argtypes = [vp, C.POINTER(dbl)]
     L.rmt_n2_campaign_step.argtypes = [vp, vp, dbl, dbl, i64, vp, vp]
     L.rmt_n2_get_profile.argtypes = [vp, C.POINTER(dbl)]
+    L.rmt_n2_set_campaign_policy.argtypes = [vp, C.POINTER(dbl), C.c_int, C.POINTER(dbl)]
+    L.rmt_n2_campaign_policy_step.argtypes = [vp, vp, dbl, dbl, i64, C.c_int, vp, vp, vp]
+    L.rmt_n2_get_campaign_level.argtypes = [vp, C.POINTER(dbl)]
     L.rmt_n2_status.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.rmt_n2_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rmt_n2_last_geometry.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -336,6 +336,14 @@ def campaign_plan(mech, N, rows=None):
     return CodePlan(cp.block, cp.npt, cp.lds_state, {**cp.defines, campaign.DEFINE: "1"}, cp.features)
 
 
+def campaign_policy_plan(mech, N, rows=None):
+    """The code object of a time-on-stream run with a "policy" (campaign.POLICY_DEFINE): the campaign unit plus
+    RMT_CAMPAIGN_POLICY - rmt_n2_campaign_policy_step beside rmt_n2_campaign_step.  A campaign without the key keeps loading
+    the unit of campaign_plan."""
+    cp = campaign_plan(mech, N, rows)
+    return CodePlan(cp.block, cp.npt, cp.lds_state, {**cp.defines, campaign.POLICY_DEFINE: "1"}, cp.features)
+
+
 def code_plans(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),
                rows=None, specialize=None, literals=None, newton=True):
     """EVERY code object a run loads, as CodePlans: the stepper's (code_plan with the same arguments, the feature "march"
@@ -415,6 +423,10 @@ def flag_error(flags):
     if f & FLAG_PRESSURE:
         return RuntimeError("model M2: the Newton sweeps of the pressure march did not converge in "
                             + where + " - pass defines={'RMT_M2_NEWTON': 4} (pressure drop > 15 % of P)")
+    if f & (campaign.FLAG_POLICY_BRACKET | campaign.FLAG_POLICY_EVALS):
+        return RuntimeError("the coolant policy of a time-on-stream step gave up (%s) in %s"
+                            % ("its bracket collapsed: the outlet jumps there" if f & campaign.FLAG_POLICY_BRACKET
+                               else "evaluation limit reached", where))
     return RuntimeError("device error in " + where)
 
 
@@ -713,6 +725,41 @@ class N2Device:
         hipbind.check(hipbind.lib().rmt_n2_campaign_step(self.h, C.c_void_p(y.data_ptr()), float(dt), float(tol),
                                                          int(max_iter), C.c_void_p(log_row.data_ptr()),
                                                          C.c_void_p(stats.data_ptr())))
+
+    def set_campaign_policy(self, rows, component, levels):
+        """Upload the policy rows [E][4] = {target, lo, hi, tolerance}, the index of the held component and the levels
+        [E] step 0 carries in (rmt_n2_set_campaign_policy: one blocking copy).  Needs the policy unit
+        (campaign_policy_plan), a profile table and a law."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        levels = np.ascontiguousarray(levels, dtype=np.float64)
+        if rows.shape != (self.E, campaign.POLICY_ROW) or levels.shape != (self.E,):
+            raise hipbind.RmtN2Error("the policy rows must be [E][4] = %r doubles and the levels [E] (got %r and %r)"
+                                     % ((self.E, 4), rows.shape, levels.shape))
+        hipbind.check(hipbind.lib().rmt_n2_set_campaign_policy(self.h, rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                                               int(component), levels.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def campaign_policy_step(self, y, dt, log_row, policy_row, stats=None, tol=initial.DEFAULTS["tolerance"],
+                             max_iter=initial.DEFAULTS["max-iterations"],
+                             max_evaluations=campaign.POLICY_DEFAULTS["max-evaluations"]):
+        """campaign_step with the coolant policy (rmt_n2_campaign_policy_step): y becomes every member's steady state at the
+        coolant level that holds the target (or at the better limit), the activities then move over ``dt`` seconds.
+        ``policy_row``: device doubles [E][4] = {level, held, marches, saturated}.  Queued on the stream, nothing is
+        synchronised."""
+        self._chk_state(y)
+        stats = self._stats if stats is None else stats
+        for t, n in ((log_row, self.E*(self.mech.V + campaign.LOG_EXTRA)), (policy_row, self.E*campaign.POLICY_LOG),
+                     (stats, self.E*4)):
+            assert t.is_cuda and t.dtype == self.torch.float64 and t.is_contiguous() and t.numel() == n, \
+                "campaign_policy_step: the log row is [E][V+6], the policy row [E][4], the stats [E][4] device doubles"
+        hipbind.check(hipbind.lib().rmt_n2_campaign_policy_step(
+            self.h, C.c_void_p(y.data_ptr()), float(dt), float(tol), int(max_iter), int(max_evaluations),
+            C.c_void_p(log_row.data_ptr()), C.c_void_p(policy_row.data_ptr()), C.c_void_p(stats.data_ptr())))
+
+    def get_campaign_level(self):
+        """The carried coolant levels [E] as they are now (rmt_n2_get_campaign_level; synchronises the stream)."""
+        out = np.zeros(self.E)
+        hipbind.check(hipbind.lib().rmt_n2_get_campaign_level(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     def get_profile(self):
         """The handle's table [E][2][N] as it is now (rmt_n2_get_profile; synchronises the stream): the activities the
@@ -1431,6 +1478,24 @@ def start_steady(dev, y, ini, mech):
     return [ini.result_entry(res[e], st["iterations"][e], st["nodes-damped"][e]) for e in range(E)]
 
 
+def policy_error(cam, e, first, plog):
+    """The exception for member ``e`` whose policy step gave up: ``plog`` [n][4] are its policy log rows from step ``first``
+    on; the first row with `saturated` 2 (bracket collapsed) or 3 (evaluation limit) is the step that failed."""
+    codes = plog[:, campaign.SATURATED].astype(np.int64)
+    bad = np.nonzero(codes >= campaign.BRACKET_COLLAPSED)[0]
+    j = int(bad[0]) if len(bad) else len(plog) - 1
+    k, row, pol = first + j, plog[j], cam.policy
+    where = ("member %d in step %d (time on stream %g s), after %d marches, at %.9g K with %s = %.12g against the target %.12g"
+             % (e, k, cam.times[k], int(row[campaign.EVALUATIONS]), row[campaign.LEVEL], pol.component,
+                row[campaign.HELD], pol.rows[e, 0]))
+    if codes[j] == campaign.BRACKET_COLLAPSED:
+        return RuntimeError("solver-config 'deactivation' 'policy': the bracket of the coolant level fell below %g K with the "
+                            "held value outside its 'tolerance' = %g: %s - the outlet jumps there, a node changed its branch "
+                            "of steady states" % (campaign.MIN_BRACKET, pol.tolerance, where))
+    return RuntimeError("solver-config 'deactivation' 'policy': 'max-evaluations' = %d reached with the held value outside "
+                        "its 'tolerance' = %g: %s" % (pol.max_evaluations, pol.tolerance, where))
+
+
 def run_campaign(modelInput, members_inputs, cam, pack_all, result):
     """solver-config "deactivation" (campaign.py): the time-on-stream run of a quasi-steady bed.  Opens the members' rows
     with the campaign unit only (campaign_plan), uploads the fresh bed's table and the law, and queues one launch of
@@ -1450,13 +1515,17 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
     E = len(inputs)
     table = prof.table() if prof is not None else np.stack([np.ones((E, zNo)), np.zeros((E, zNo))], axis=1)
     IV = plan.initial_states(named, mech, zNo, plan.initial_state)
-    cp = campaign_plan(mech, zNo, rows)
+    pol = cam.policy
+    cp = campaign_plan(mech, zNo, rows) if pol is None else campaign_policy_plan(mech, zNo, rows)
     dev = device_cls()(mech, rows, zNo, block=cp.block, npt=cp.npt, defines=cp.defines, specialize=False,
                        features=cp.features, profile=table)
     try:
         import torch
         dev.set_campaign_law(cam.law)
         y = dev.to_device(IV)
+        if pol is not None:                # the policy unit: the rows, and ONE more device buffer beside the log
+            dev.set_campaign_policy(pol.rows, pol.index, pol.levels)
+            plog = torch.zeros((cam.K + 1, E, campaign.POLICY_LOG), dtype=torch.float64, device=y.device)
         log = torch.zeros((cam.K + 1, E, mech.V + campaign.LOG_EXTRA), dtype=torch.float64, device=y.device)
         stats = torch.zeros((cam.K + 1, E, 4), dtype=torch.float64, device=y.device)
         marks = {int(k): i for i, k in enumerate(cam.output_steps)}
@@ -1464,7 +1533,11 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
         for k, dt in enumerate(cam.dts()):
             if k in marks:
                 acts.append(dev.get_profile()[:, 0] if k else table[:, 0].copy())       # a(t_k): launch k moves it on
-            dev.campaign_step(y, dt, log[k], stats[k], cam.tolerance, cam.max_iterations)
+            if pol is None:
+                dev.campaign_step(y, dt, log[k], stats[k], cam.tolerance, cam.max_iterations)
+            else:
+                dev.campaign_policy_step(y, dt, log[k], plog[k], stats[k], cam.tolerance, cam.max_iterations,
+                                         pol.max_evaluations)
             if k not in marks:
                 continue
             Yh = y.cpu().numpy()
@@ -1472,6 +1545,8 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
             err = flag_error(flags)
             if err is not None:
                 e = int(np.nonzero(flags)[0][0])
+                if int(flags[e]) & (campaign.FLAG_POLICY_BRACKET | campaign.FLAG_POLICY_EVALS):
+                    raise policy_error(cam, e, checked, plog[checked:k + 1, e].cpu().numpy())
                 st = stats[checked:k + 1, e].cpu().numpy()
                 bad = np.nonzero(st[:, 1] >= 0)[0]
                 j = int(bad[0]) if len(bad) else len(st) - 1
@@ -1483,6 +1558,7 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
             for e, pk in enumerate(pack_all(Yh, named, mech, zNo, float(cam.times[k]))):
                 packs[e].append(pk)
         logs = log.cpu().numpy()
+        plogs = plog.cpu().numpy() if pol is not None else None
         raw = stats.cpu().numpy()
         dstats = {"launches": cam.K + 1, "steps": cam.K, "march-iterations": int(step_counts(raw.reshape(-1, 4))[0].max()),
                   "nodes-damped": int(step_counts(raw.reshape(-1, 4))[1].sum())}
@@ -1490,6 +1566,9 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
         dev.close()
     acts = np.array(acts)                                                   # [n_out+1][E][N]
     entries = [campaign.result_entry(cam, e, logs[:, e], acts[:, e], mech, zNo, named[e]) for e in range(E)]
+    if pol is not None:
+        for e, entry in enumerate(entries):
+            entry[campaign.POLICY] = campaign.policy_entry(cam, e, plogs[:, e])
     res = result(packs[0], modelInput, zNo, cam.outputs)
     res["computation-time"] = np.round(timer() - start, ROUND_FUN_ACCURACY)
     res["device-stats"] = dstats

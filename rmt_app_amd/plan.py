@@ -304,6 +304,8 @@ class Mechanism:
         if "RMT_KINETICS_SOURCE" not in template:
             raise ValueError("kernel template lacks the RMT_KINETICS_SOURCE marker")
         if str((defines or {}).get("RMT_CAMPAIGN", "0")) != "1":
+            if str((defines or {}).get("RMT_CAMPAIGN_POLICY", "0")) != "0":
+                raise ValueError("RMT_CAMPAIGN_POLICY: only together with RMT_CAMPAIGN=1 (n2.campaign_policy_plan)")
             template = without_campaign(template)
         # one reciprocal for the independent divisions of the rate laws (lowering.Lowered.div_groups).  RMT_DIV_BATCH is
         # a switch of this generator, not a macro the kernel source reads: 0 switches the pass off.  Not in a unit that

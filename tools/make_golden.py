@@ -5,12 +5,12 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign policy  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
 coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
 closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|syn12]: discrete steady states of model N2,
 G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18; campaign[=DA|DB|DC|DI]:
-time-on-stream runs with catalyst deactivation, G19 - like G13..G15 these
+time-on-stream runs with catalyst deactivation, G19; policy[=PA|PS|PB]: the coolant policy of such a run, G20 - like G13..G15 these
 run SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
@@ -1474,6 +1474,41 @@ def g_campaign(which=None):
             name, time.time() - t0, out["residual"].max(), out["activity"][-1].min(), out["activity"][-1].max()), flush=True)
 
 
+# ------------------------------------------------------------------ G20: the coolant policy of a time-on-stream run
+# (solver-config "deactivation" "policy").  tests/policy_ref.py: per step scipy.optimize.brentq on r(T) = x_c,outlet(T) -
+# target, every value a steady state of the profiled right-hand side of G18 with the uniform coolant offset T - MeTe, the
+# saturation rule restated, the law of G19.  A case is refused (SystemExit) when a steady state ends above the gate of G17,
+# when r at 9 equidistant levels changes sign more than once in a step, or when two adjacent samples differ by more than
+# 20 x the median difference.
+def g_policy(which=None):
+    import policy_ref as PO
+    from oracle import n2_oracle as O
+    path = os.path.join(GOLD, "g20_policy.json")
+    meta = {"cases": {}, "gate": PO.CR.GATE, "xtol": PO.XTOL, "samples": PO.SAMPLES, "jump": PO.JUMP,
+            "reference": "per step scipy.optimize.brentq (xtol 1e-10 K) on r(T) = x_c,outlet(T) - target within the limits, "
+                         "every value a steady state of profile_ref.profiled_rhs with the uniform coolant offset T - MeTe "
+                         "(campaign_ref.steady_state from the nearest known state), no sign change between the limits: the "
+                         "limit with the smaller |r| (a tie: lo); the activity moved by campaign_ref.law_update "
+                         "(tests/policy_ref.py)"}
+    for name in ([which] if which else list(PO.CASES)):
+        case = PO.CASES[name]
+        t0 = time.time()
+        out = PO.run_case(O, INP, case, log=lambda msg: print("G20 %s: %s" % (name, msg), flush=True))
+        np.savez_compressed(os.path.join(GOLD, "g20_policy_%s.npz" % name), times=out["times"], marks=out["marks"],
+                            activity=out["activity"], states=out["states"], level=out["level"], held=out["held"],
+                            saturated=out["saturated"], sample_levels=out["sample_levels"], samples=out["samples"],
+                            residual=out["residual"], delta=out["delta"])
+        if os.path.exists(path):           # (read again: the cases may be made by several processes)
+            with open(path) as fh:
+                meta["cases"] = json.load(fh)["cases"]
+        meta["cases"][name] = dict(case, residual=float(out["residual"].max()), level=[float(v) for v in out["level"]],
+                                   saturated=[int(v) for v in out["saturated"]])
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+        print("G20 %s written (%.0f s): levels %s, saturated %s" % (name, time.time() - t0, out["level"], out["saturated"]),
+              flush=True)
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1513,6 +1548,8 @@ def main(argv):
             g_profile(what.split("=", 1)[1] if "=" in what else None)
         elif what == "campaign" or what.startswith("campaign="):
             g_campaign(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "policy" or what.startswith("policy="):
+            g_policy(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

@@ -207,6 +207,17 @@ int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* out, int nout
  * rejected = the number of nodes that needed a rejected step.  A member whose march fails (a node at max_iter, a
  * non-finite state, a zero pivot) gets RMT_N2_FLAG_STEP / RMT_N2_FLAG_NONFINITE and keeps the input downstream of it. */
 int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, int64_t max_iter, rmt_n2_stats* stats_out);
+/* Parametric sensitivities of that steady state (solver-config "sensitivity", csrc/kernels/73_sensitivity.inc): y DEVICE
+ * double [E][V][N] is the converged state rmt_n2_steady_march left, out DEVICE double [E][n_params][V+1][N] receives per
+ * member and parameter the rows d y_v,z / dp (v < V, in the scaled units of the state) and d P_z / dp (row V).  The
+ * parameters are values of the member's device row: kinds[p] = 0 TM, 1 THETA_IN, 2 P0 (indices[p] = 0), 3 CIN[indices[p]],
+ * 4 the user column indices[p]; kinds and indices are HOST arrays of n_params ints, 1 <= n_params <= 8.  All derivatives
+ * are analytic (the tangent system of the block lower-bidiagonal steady state is a downstream march as well: one V x V
+ * inverse per node, applied to every right-hand side).  Needs a code object generated with RMT_SENS 1 and
+ * RMT_SENS_NP == n_params beside RMT_WITH_MARCH, else it returns an error (a mismatch of n_params that only the kernel
+ * can see flags every member).  Enqueues ONE kernel on the handle's stream and does not synchronise.  A member with a
+ * singular node gets RMT_N2_FLAG_NONFINITE and NaN in its rows at that node; the nodes behind it are not written. */
+int rmt_n2_steady_sens(rmt_n2_handle* h, const void* y, int n_params, const int* kinds, const int* indices, double* out);
 /* Time-on-stream campaigns (solver-config "deactivation", csrc/kernels/72_campaign.inc): the bed is quasi-steady, its
  * catalyst activity a_n follows da_n/dt = -k_d(T_n) (a_n - a_inf)^m, k_d(T) = k_ref exp(-(Ed/R)(1/T - 1/Tref)), T_n the
  * node's temperature in kelvin (the member's inlet temperature in an iso-thermal run).  The three calls need a handle whose

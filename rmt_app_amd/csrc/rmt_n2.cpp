@@ -61,7 +61,7 @@ struct rmt_n2_handle {
     hipFunction_t f_rhs = nullptr, f_rk4_reg = nullptr, f_rk4_mem = nullptr, f_rk45_reg = nullptr,
                   f_rk45_mem = nullptr, f_multistep = nullptr, f_rk4_chain = nullptr, f_ros4 = nullptr, f_n1 = nullptr,
                   f_ros4_chain = nullptr, f_rk45_chain = nullptr, f_rk4_redo = nullptr, f_rk4_chain_redo = nullptr,
-                  f_march = nullptr, f_campaign = nullptr, f_policy = nullptr;
+                  f_march = nullptr, f_campaign = nullptr, f_policy = nullptr, f_sens = nullptr;
     unsigned long long* d_rings = nullptr;   // tagged-word links of the chained stiff stepper: rings, decision slots, abort words
     size_t ring_bytes = 0;
     double* d_members1 = nullptr;
@@ -271,6 +271,7 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
         {"rmt_n2_steady_march", &rmt_n2_handle::f_march, false},
         {"rmt_n2_campaign_step", &rmt_n2_handle::f_campaign, false},
         {"rmt_n2_campaign_policy_step", &rmt_n2_handle::f_policy, false},
+        {"rmt_n2_steady_sens", &rmt_n2_handle::f_sens, false},
     };
     for (const auto& k : kernels) {
         const hipError_t e = hipModuleGetFunction(&(h->*k.f), h->module, k.name);
@@ -781,6 +782,40 @@ extern "C" int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, in
     // one reactor per lane, one wave per workgroup (the shape of rmt_n1_ros4)
     HIP_OK(hipEventRecord(h->ev0, h->stream));
     HIP_OK(hipModuleLaunchKernel(h->f_march, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    HIP_OK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return 0;
+}
+
+// solver-config "sensitivity" (kernels/73_sensitivity.inc): the tangent march over the converged state, behind
+// rmt_n2_steady_march on the same handle.  The descriptor travels by value: {kind[8], index[8]} as the kernel declares it.
+#define RMT_N2_SENS_MAX 8
+extern "C" int rmt_n2_steady_sens(rmt_n2_handle* h, const void* y, int n_params, const int* kinds, const int* indices,
+                                  double* out) {
+    if (!h || !y || !kinds || !indices || !out) return fail("rmt_n2_steady_sens: null argument");
+    if (!h->f_sens || !h->f_march)
+        return fail("rmt_n2_steady_sens: this handle's code object has no rmt_n2_steady_sens (generate it with RMT_SENS and "
+                    "RMT_SENS_NP beside RMT_WITH_MARCH)");
+    if (h->fp32) return fail("rmt_n2_steady_sens: fp64 only");
+    if (n_params < 1 || n_params > RMT_N2_SENS_MAX) return fail("rmt_n2_steady_sens: 1..8 parameters (got %d)", n_params);
+    struct { int kind[RMT_N2_SENS_MAX], index[RMT_N2_SENS_MAX]; } desc;
+    std::memset(&desc, 0, sizeof(desc));
+    for (int p = 0; p < n_params; ++p) {
+        const int k = kinds[p], i = indices[p];
+        if (k < 0 || k > 4 || i < 0 || (k == 3 && i >= h->S) || (k == 4 && i >= h->NU) || (k < 3 && i != 0))
+            return fail("rmt_n2_steady_sens: parameter %d: kind %d (0 TM, 1 THETA_IN, 2 P0, 3 CIN[index], 4 user column "
+                        "[index]) with index %d is out of range (S = %d, NU = %d)", p, k, i, h->S, h->NU);
+        desc.kind[p] = k;
+        desc.index[p] = i;
+    }
+    PROFILE_READY(h);
+    ON_DEVICE(h);
+    int N = h->N, E = h->E;
+    void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&n_params, (void*)&desc, (void*)&out,
+                    (void*)&h->d_flags};
+    // one reactor per lane, one wave per workgroup (the shape of rmt_n2_steady_march)
+    HIP_OK(hipEventRecord(h->ev0, h->stream));
+    HIP_OK(hipModuleLaunchKernel(h->f_sens, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
     HIP_OK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     return 0;

@@ -1479,10 +1479,12 @@ class Gradient(Lowered):
             pos += len(p)
         return vals[:R], out
 
-    def emit_jac(self, fname="rmt_kinetics_jac", with_p=False):
+    def emit_jac(self, fname="rmt_kinetics_jac", with_p=False, with_u=None):
         """Device function: rates r[R] and the partials drdT[R], drdx[R][S], drdC[R][S] (zeros written
         as literals, which the compiler then removes from the chain rule of the node Jacobian); with_p: also
-        drdP[R] (model N1, where the pressure is a state variable - the gradient must have been taken by "P" too)."""
+        drdP[R] (model N1, where the pressure is a state variable - the gradient must have been taken by "P" too);
+        with_u = NU (not None): also drdU[R][max(NU, 1)], the partials by the per-reactor inputs u<k> (the sensitivity
+        sweep - the gradient must have been taken by them too)."""
         lines, name = self._emit_body(nocheck_from=self.n_primal)
         S, R = self.S, self.n_rates
         outs = ["    r[%d] = %s;" % (k, name[o]) for k, o in enumerate(self.rate_outputs)]
@@ -1493,6 +1495,8 @@ class Gradient(Lowered):
             for i in range(S):
                 outs.append("    drdx[%d][%d] = %s;" % (q, i, name[p["x%d" % i]] if ("x%d" % i) in p else "real(0)"))
                 outs.append("    drdC[%d][%d] = %s;" % (q, i, name[p["C%d" % i]] if ("C%d" % i) in p else "real(0)"))
+            for k in range(max(with_u, 1) if with_u is not None else 0):
+                outs.append("    drdU[%d][%d] = %s;" % (q, k, name[p["u%d" % k]] if ("u%d" % k) in p else "real(0)"))
         return (
             "template <typename FL>\n"
             "__device__ __forceinline__ void %s(const real T, const real invT, const real P,\n"
@@ -1500,7 +1504,9 @@ class Gradient(Lowered):
             "        real* __restrict__ r,\n"
             "        real* __restrict__ drdT, real (*__restrict__ drdx)[RMT_S], real (*__restrict__ drdC)[RMT_S],%s FL& flag) {\n"
             "    (void)invT; (void)U;\n%s\n%s\n}\n"
-            % (fname, " real* __restrict__ drdP," if with_p else "", "\n".join(lines), "\n".join(outs)))
+            % (fname, (" real* __restrict__ drdP," if with_p else "")
+               + (" real (*__restrict__ drdU)[RMT_NU > 0 ? RMT_NU : 1]," if with_u is not None else ""),
+               "\n".join(lines), "\n".join(outs)))
 
 
 def is_scalar_constant(v):

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from . import campaign, control, hipbind, initial, launches, monitor, plan, profile, schedule
+from . import campaign, control, hipbind, initial, launches, monitor, plan, profile, schedule, sensitivity
 from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
@@ -344,6 +344,18 @@ def campaign_policy_plan(mech, N, rows=None):
     return CodePlan(cp.block, cp.npt, cp.lds_state, {**cp.defines, campaign.POLICY_DEFINE: "1"}, cp.features)
 
 
+def sens_plan(mech, N, n_params, defines=None, rows=None):
+    """The code object of a run with solver-config "sensitivity" (csrc/kernels/73_sensitivity.inc): whatever march_plan
+    gives for the run (forced or profiled rows) plus RMT_SENS and RMT_SENS_NP - rmt_n2_steady_sens beside
+    rmt_n2_steady_march.  ``mech``: the mechanism of the sensitivity unit (the "rate-constant" parameters among its
+    per-reactor inputs).  It takes the place of the march unit on the march handle (N2Device.attach_march: where its
+    mechanism is the run's own; else it gets a handle of its own beside the plain march unit); every other unit of the
+    run is what it is without the key."""
+    cp = march_plan(mech, N, defines, rows)
+    return CodePlan(cp.block, cp.npt, cp.lds_state,
+                    {**cp.defines, sensitivity.DEFINE: "1", sensitivity.DEFINE_NP: str(int(n_params))}, cp.features)
+
+
 def code_plans(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),
                rows=None, specialize=None, literals=None, newton=True):
     """EVERY code object a run loads, as CodePlans: the stepper's (code_plan with the same arguments, the feature "march"
@@ -513,6 +525,7 @@ class N2Device:
         self.dtype = torch.float32 if self.fp32 else torch.float64
         self._stats = torch.zeros((self.E, 4), dtype=torch.float64, device=self.device)
         self.march = None       # a second device of the same rows with the steady-state march (attach_march)
+        self.sens = None        # ... and a third with the sensitivity unit, where that needs a mechanism of its own
         self.use_current_stream()
         self.profile = None
         if profile is not None:
@@ -563,6 +576,8 @@ class N2Device:
         self.profile = table
         if self.march is not None:
             self.march.set_profile(table)
+        if self.sens is not None:
+            self.sens.set_profile(table)
 
     def get_members(self):
         """The device rows as they are now [E][row_width] (synchronises the stream): what the last refresh uploaded and
@@ -581,6 +596,9 @@ class N2Device:
         if getattr(self, "march", None) is not None:
             self.march.close()
             self.march = None
+        if getattr(self, "sens", None) is not None:
+            self.sens.close()
+            self.sens = None
         if getattr(self, "h", None):
             hipbind.lib().rmt_n2_destroy(self.h)
             self.h = None
@@ -666,16 +684,60 @@ class N2Device:
                                                 float(rtol), float(atol), float(h0), int(max_steps),
                                                 C.c_void_p(self._stats.data_ptr())))
 
-    def attach_march(self):
+    def attach_march(self, sens=None):
         """A second handle on the same member rows whose code object holds the steady-state march (march_plan): the
-        stepper's own code object stays what it is without it.  steady_march / march_result then go through it."""
+        stepper's own code object stays what it is without it.  steady_march / march_result then go through it.
+        ``sens`` = (n_params, mechanism, rows) (solver-config "sensitivity"): with the run's own mechanism the handle's code
+        object is the sensitivity unit (sens_plan) - the march kernel in it is the march unit's text - and steady_sens goes
+        through it as well.  With another mechanism (a "rate-constant" the run keeps a literal is a per-reactor input
+        there, the rows are widened by it) the march stays on the plain march unit, so that the started state is the one
+        of the run without the key, and a third handle holds the sensitivity unit for steady_sens alone."""
         if "march" not in self.features and self.march is None:
             if self.fp32 or getattr(self.mech, "model", "N2") != "N2":
                 raise hipbind.RmtN2Error("the steady-state march is for model N2 in fp64")
-            cp = march_plan(self.mech, self.N, self.defines, self.members)
-            self.march = N2Device(self.mech, self.members, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
+            if sens is None or sens[1] is not self.mech:
+                mech, rows, cp = self.mech, self.members, march_plan(self.mech, self.N, self.defines, self.members)
+            else:
+                n_params, mech, rows = sens
+                cp = sens_plan(mech, self.N, n_params, self.defines, rows)
+            self.march = N2Device(mech, rows, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
                                   defines=cp.defines, specialize=False, features=cp.features, profile=self.profile)
+            if sens is not None and sens[1] is not self.mech:
+                n_params, mech, rows = sens
+                cp = sens_plan(mech, self.N, n_params, self.defines, rows)
+                self.sens = N2Device(mech, rows, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
+                                     defines=cp.defines, specialize=False, features=cp.features, profile=self.profile)
         return self
+
+    def steady_sens(self, y, kinds, indices):
+        """Parametric sensitivities of the steady state y (rmt_n2_steady_sens, behind steady_march on the same handle):
+        returns the device tensor [E][NP][V+1][N] - per member and parameter d(scaled state)/d(row value) and, in row V,
+        dP/d(row value).  ``kinds`` / ``indices``: sensitivity.Sensitivity.descriptors.  Queued on the stream, nothing is
+        synchronised; status() reads the flags.  Needs a code object of sens_plan with RMT_SENS_NP = len(kinds)."""
+        if self.sens is not None:
+            return self.sens.steady_sens(y, kinds, indices)
+        if "march" not in self.features and self.march is not None:
+            return self.march.steady_sens(y, kinds, indices)
+        self._chk_state(y)
+        if str(self.defines.get(sensitivity.DEFINE, "0")) != "1" or int(self.defines[sensitivity.DEFINE_NP]) != len(kinds):
+            raise hipbind.RmtN2Error("steady_sens needs the sensitivity unit (sens_plan) with RMT_SENS_NP = %d" % len(kinds))
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        assert kinds.shape == indices.shape and kinds.ndim == 1
+        out = self.torch.zeros((self.E, len(kinds), self.mech.V + 1, self.N), dtype=self.torch.float64, device=self.device)
+        hipbind.check(hipbind.lib().rmt_n2_steady_sens(self.h, C.c_void_p(y.data_ptr()), len(kinds),
+                                                       kinds.ctypes.data_as(C.POINTER(C.c_int)),
+                                                       indices.ctypes.data_as(C.POINTER(C.c_int)),
+                                                       C.c_void_p(out.data_ptr())))
+        return out
+
+    def sens_status(self):
+        """The status words of the handle steady_sens ran on, read and cleared (synchronises)."""
+        if self.sens is not None:
+            return self.sens.status()
+        if "march" not in self.features and self.march is not None:
+            return self.march.status()
+        return self.status()
 
     def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
         """In place: every member's state becomes the discrete steady state f(y) = 0 of its device rows (a forced row: its
@@ -873,9 +935,15 @@ class AutoStepper:
     def rk45_stats(self):
         return self.last.rk45_stats()
 
-    def attach_march(self):
-        self.d45.attach_march()
+    def attach_march(self, sens=None):
+        self.d45.attach_march(sens)
         return self
+
+    def steady_sens(self, y, kinds, indices):
+        return self.d45.steady_sens(y, kinds, indices)
+
+    def sens_status(self):
+        return self.d45.sens_status()
 
     def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
         """the steady-state march on the rows of the explicit device (both devices hold the same rows)"""
@@ -1080,7 +1148,7 @@ def mechanism_for(modelInput, inputs, cfg):
 
 
 def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=None, npt=None, defines=None,
-                 features=(), forcing=None, march=False, prof=None):
+                 features=(), forcing=None, march=False, prof=None, sens=None):
     """Device + initial state for the members THIS process integrates.
 
     Single process: all of ``inputs``.  As one rank of a torch.distributed job (``sync``, see
@@ -1090,7 +1158,8 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     ``forcing`` (a Forcing, solver-config "schedule"): the code object is generated with RMT_FORCING (2 when the schedule
     moves the feed composition, else 1), the rows get their tail, and the host fixes the kernel form (forced_mode).
     ``march`` (solver-config "initial", single process): a second handle on the same rows holds the steady-state march
-    (N2Device.attach_march).
+    (N2Device.attach_march); with ``sens`` (a sensitivity.Sensitivity, solver-config "sensitivity") that handle's code
+    object is the sensitivity unit (sens_plan) and ``sens.mech`` / ``sens.rows`` receive its mechanism and rows.
     ``prof`` (a profile.Profile, solver-config "axial-profile", single process): the code object is generated with
     RMT_PROFILE, the table is uploaded before anything is launched, and the host fixes the kernel form by the rule of the
     forced runs (no chained form carries the profile)."""
@@ -1117,7 +1186,11 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
             dev.set_mode(mode)
         if march:
             try:
-                dev.attach_march()
+                if sens is not None:
+                    sens.mech = mech if sens.unit_params(mech.params) == tuple(mech.params) \
+                        else plan.Mechanism(inputs[0], params=sens.unit_params(mech.params))
+                    sens.rows = sens.widen(rows, mech, sens.mech, inputs)
+                dev.attach_march(None if sens is None else (sens.NP, sens.mech, sens.rows))
             except Exception:
                 dev.close()
                 raise
@@ -1147,7 +1220,7 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
 
 
 def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None, forcing=None, march=False,
-              prof=None):
+              prof=None, sens=None):
     """The two devices of ivp "hip-auto" (explicit pair in its on-chip geometry, Rosenbrock family) behind one
     AutoStepper; an explicit `block` / `nodes-per-thread` of the solver-config applies to the explicit device."""
     if block is None and (forcing is not None or prof is not None):       # (no chained chunks: they carry neither)
@@ -1157,7 +1230,8 @@ def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, np
     else:
         b45, n45, d45 = block, npt, {}
     dev45, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=b45, npt=n45,
-                                          defines={**(defines or {}), **d45}, forcing=forcing, march=march, prof=prof)
+                                          defines={**(defines or {}), **d45}, forcing=forcing, march=march, prof=prof,
+                                          sens=sens)
     def make_ros4():
         return open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=ros4_block(mech.V, zNo, fp32),
                             npt=1, defines=defines, features=("ros4",), forcing=forcing, prof=prof)[0]
@@ -1478,6 +1552,22 @@ def start_steady(dev, y, ini, mech):
     return [ini.result_entry(res[e], st["iterations"][e], st["nodes-damped"][e]) for e in range(E)]
 
 
+def start_sensitivity(dev, y, sens, named):
+    """solver-config "sensitivity": ONE launch of rmt_n2_steady_sens on the march handle behind the march that made y, the
+    buffer [E][NP][V+1][N] comes back once.  Raises FloatingPointError naming the member and the node when a node of the
+    tangent march is singular.  Returns the members' result entries."""
+    kinds, indices = sens.descriptors(sens.mech)
+    raw = dev.steady_sens(y, kinds, indices).cpu().numpy()
+    flags = dev.sens_status()
+    if np.any(flags):
+        e = int(np.nonzero(flags)[0][0])
+        raise FloatingPointError("solver-config 'sensitivity': the node Jacobian is singular (or a sensitivity is not "
+                                 "finite) at node %d of member %d (flags=0x%x)"
+                                 % (sensitivity.failed_node(raw[e]), e, int(flags[e])))
+    Yh = y.cpu().numpy()
+    return [sensitivity.result_entry(sens, raw[e], Yh[e], sens.rows[e], named[e], sens.mech) for e in range(raw.shape[0])]
+
+
 def policy_error(cam, e, first, plog):
     """The exception for member ``e`` whose policy step gave up: ``plog`` [n][4] are its policy log rows from step ``first``
     on; the first row with `saturated` 2 (bracket collapsed) or 3 (evaluation limit) is the step that failed."""
@@ -1625,6 +1715,9 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
     # without it
     profile.check_model(modelInput)
     prof = profile.parse(modelInput, members_inputs, ivp, sync is not None) if with_schedule else None
+    # "sensitivity": parametric sensitivities of the steady state the run starts from (sensitivity.py); absent = None =
+    # exactly the run without it
+    sens = sensitivity.parse(modelInput, members_inputs, sync is not None) if with_schedule else None
     # the ONE launch list of the run; a sample that fell on a mark carries that mark's time from here on (result entries)
     walk, sample_times, control_times = launches.merge(
         opT, tNo, forced_by.times if forced_by is not None else (), mon.times if mon is not None else None,
@@ -1661,11 +1754,11 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         defines.update(geo_defs)
     if ivp == "hip-auto":
         dev, named_local, IV = open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block, npt, forcing=forcing,
-                                         march=ini is not None, prof=prof)
+                                         march=ini is not None, prof=prof, sens=sens)
     else:
         dev, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=block, npt=npt,
                                             defines=defines, features=("ros4",) if ivp == "hip-ros4" else (),
-                                            forcing=forcing, march=ini is not None, prof=prof)
+                                            forcing=forcing, march=ini is not None, prof=prof, sens=sens)
     # the process that returns the results (rank 0, or the only one) packs EVERY member
     packer = sync is None or sync.rank == 0
     try:
@@ -1676,6 +1769,7 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         y = guarded(sync, dev.to_device, IV)
         # (the device rows are those of t = 0: a forced run's were attached for its first launch, which starts there)
         started = start_steady(dev, y, ini, mech) if ini is not None else None
+        sensed = start_sensitivity(dev, y, sens, named) if sens is not None else None
         packs = [[] for _ in named]
 
         def on_interval(i, t1, Yh):
@@ -1723,6 +1817,11 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         if members_inputs:
             for entry, st in zip(res["ensemble"], started):
                 entry["initial"] = st
+    if sensed is not None:
+        res[sensitivity.KEY] = sensed[0]
+        if members_inputs:
+            for entry, se in zip(res["ensemble"], sensed):
+                entry[sensitivity.KEY] = se
     if monitors:
         res["monitor"] = monitors[0]
         if members_inputs:
@@ -1749,6 +1848,7 @@ def run_n2(modelInput, members_inputs=None):
         if len(named) == 1 and not outlet:
             return [pack_interval(Yg[0], named[0], mech, zNo, t1, modelId)]
         return pack_intervals(Yg, named, mech, zNo, t1, modelId)
+    sensitivity.parse(modelInput, members_inputs)      # (validation before any device work: not with "deactivation")
     # "deactivation": a time-on-stream run of the quasi-steady bed (campaign.py) - no integration in time; absent = None =
     # exactly the run without it
     cam = campaign.parse(modelInput, members_inputs, active_ranks(len(members_inputs)) is not None if members_inputs else False)

@@ -300,13 +300,21 @@ class Mechanism:
     def source(self, template, fp32=False, block=1024, npt=1, lds_state=None, defines=None):
         """Complete translation unit: prelude + template with the lowered kinetics spliced in.  The text of the campaign
         step (csrc/kernels/72_campaign.inc, between its two marks) goes into the campaign unit only (RMT_CAMPAIGN): every
-        other unit's source, and with it its cache key, is what it is without that file."""
+        other unit's source, and with it its cache key, is what it is without that file.  The same holds for the text of
+        the sensitivity sweep (csrc/kernels/73_sensitivity.inc) and the sensitivity unit (RMT_SENS)."""
         if "RMT_KINETICS_SOURCE" not in template:
             raise ValueError("kernel template lacks the RMT_KINETICS_SOURCE marker")
+        # ... and the text of the sensitivity sweep (csrc/kernels/73_sensitivity.inc, between its two marks) into the
+        # sensitivity unit only (RMT_SENS, n2.sens_plan)
+        sens = str((defines or {}).get("RMT_SENS", "0")) == "1"
+        if not sens:
+            if str((defines or {}).get("RMT_SENS_NP", "0")) != "0":
+                raise ValueError("RMT_SENS_NP: only together with RMT_SENS=1 (n2.sens_plan)")
+            template = _cut(template, SENS_MARKS)
         if str((defines or {}).get("RMT_CAMPAIGN", "0")) != "1":
             if str((defines or {}).get("RMT_CAMPAIGN_POLICY", "0")) != "0":
                 raise ValueError("RMT_CAMPAIGN_POLICY: only together with RMT_CAMPAIGN=1 (n2.campaign_policy_plan)")
-            template = without_campaign(template)
+            template = _cut(template, CAMPAIGN_MARKS)
         # one reciprocal for the independent divisions of the rate laws (lowering.Lowered.div_groups).  RMT_DIV_BATCH is
         # a switch of this generator, not a macro the kernel source reads: 0 switches the pass off.  Not in a unit that
         # also prints the gradient DAG (the same two conditions as below): the stiff and the steady steppers take the
@@ -334,6 +342,14 @@ class Mechanism:
             dag = self.device_dag()
             wrt = sorted({dag.g.nodes[i][1] for i in dag.live if dag.g.nodes[i][0] == "in"})
             kin += dag.gradient(wrt=wrt).emit_jac("rmt_kinetics_jacp", with_p=True)
+        if sens:
+            # the sensitivity sweep: rmt_kinetics_jac plus the partials by P and by EVERY per-reactor input u<k> of the
+            # unit's mechanism (one gradient DAG; a column nobody asks for is dead code to the compiler)
+            dag = self.device_dag()
+            base = sorted({dag.g.nodes[i][1] for i in dag.live if dag.g.nodes[i][0] == "in" and dag.g.nodes[i][1] != "P"
+                           and dag.g.nodes[i][1][0] != "u"})
+            kin += dag.gradient(wrt=base + ["P"] + ["u%d" % k for k in range(self.NU)]).emit_jac(
+                "rmt_kinetics_jacs", with_p=True, with_u=self.NU)
         body = template.replace("RMT_KINETICS_SOURCE", kin, 1)
         return self.prelude(fp32, block, npt, lds_state, defines) + body
 
@@ -392,13 +408,23 @@ class Mechanism:
 CAMPAIGN_MARKS = ("//>>> RMT_CAMPAIGN", "//<<< RMT_CAMPAIGN\n")
 
 
-def without_campaign(template):
-    """The device template without the text of csrc/kernels/72_campaign.inc (from its opening mark to the end of its
-    closing one); a template that has no such text comes back as it is."""
-    lo, hi = template.find(CAMPAIGN_MARKS[0]), template.find(CAMPAIGN_MARKS[1])
+SENS_MARKS = ("//>>> RMT_SENS", "//<<< RMT_SENS\n")
+
+
+def _cut(template, marks):
+    """The template without the text from the opening mark to the end of the closing one; a template that has no such
+    text comes back as it is."""
+    lo, hi = template.find(marks[0]), template.find(marks[1])
     if lo < 0 or hi < lo:
         return template
-    return template[:lo] + template[hi + len(CAMPAIGN_MARKS[1]):]
+    return template[:lo] + template[hi + len(marks[1]):]
+
+
+def without_campaign(template):
+    """The device template of an ordinary unit: without the text of the files that go into one unit each -
+    csrc/kernels/72_campaign.inc and csrc/kernels/73_sensitivity.inc, each from its opening mark to the end of its closing
+    one; a template that has no such text comes back as it is."""
+    return _cut(_cut(template, SENS_MARKS), CAMPAIGN_MARKS)
 
 
 GAMACOTE_N2_ERROR = "setting an array element with a sequence."

@@ -30,6 +30,8 @@ def rmtExe(modelInput):
         if modelType != "N2" and modelInput['solver-config'].get('schedule') is not None:
             raise ValueError("solver-config 'schedule' (time-varying inlet / coolant conditions) is only available for "
                              "model 'N2' (got model %r)" % (modelType,))
+        from .sensitivity import check_model as check_sensitivity
+        check_sensitivity(modelInput)         # solver-config 'sensitivity': model N2 only (needs 'initial': asked first)
         from .monitor import check_model
         check_model(modelInput)               # solver-config 'monitor': models N2 and M2 only
         from .control import check_model as check_control

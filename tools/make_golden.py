@@ -5,12 +5,13 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign policy  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign policy sensitivity  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
 coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
 closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|syn12]: discrete steady states of model N2,
 G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18; campaign[=DA|DB|DC|DI]:
-time-on-stream runs with catalyst deactivation, G19; policy[=PA|PS|PB]: the coolant policy of such a run, G20 - like G13..G15 these
+time-on-stream runs with catalyst deactivation, G19; policy[=PA|PS|PB]: the coolant policy of such a run, G20;
+sensitivity[=SA|SB|SK|SW]: parametric sensitivities of the steady state, G21 - like G13..G15 these
 run SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
@@ -1509,6 +1510,49 @@ def g_policy(which=None):
               flush=True)
 
 
+# ------------------------------------------------------------------ G21: parametric sensitivities of the N2 steady state
+# (solver-config "sensitivity", rmt_app_amd/sensitivity.py).  tests/sens_ref.py: Richardson-extrapolated central differences
+# of steady states of the oracle's right-hand side with ONE value moved, each found by the recipe and under the gate of
+# G17 / G18; nothing of the product is imported.  The step starts at 1e-4 |p| (a concentration: 1e-4 of the largest feed
+# concentration); a case whose fd_error = max|D(d/2) - D(d)| exceeds 1e-5 of a row's largest magnitude is refused
+# (SystemExit) - move the step of that parameter within [1e-5, 1e-3] |p| (G21_DELTAS), not the cap.
+G21_DELTAS = {}          # case -> {parameter label: relative step}; empty: every parameter at sens_ref.DELTA0
+
+
+def g_sensitivity(which=None):
+    import sens_ref as SR
+    from oracle import n2_oracle as O
+    path = os.path.join(GOLD, "g21_sensitivity.json")
+    meta = {"cases": {}, "gate": SR.CR.GATE, "fd_cap": SR.FD_CAP,
+            "reference": "central differences at d and d/2 of steady states of oracle.n2_oracle.make_rhs_vec (bed A: "
+                         "profile_ref.profiled_rhs) with one value moved, each from campaign_ref.steady_state and a Newton "
+                         "polish, D = (4 D(d/2) - D(d))/3, fd_error = max|D(d/2) - D(d)| per (parameter, row) "
+                         "(tests/sens_ref.py)"}
+    for name in ([which] if which else list(SR.CASES)):
+        for rel in G21_DELTAS.get(name, {}).values():
+            assert 1e-5 <= rel <= 1e-3
+        t0 = time.time()
+        out = SR.run_case(O, INP, name, G21_DELTAS.get(name), log=lambda msg: print("G21 %s" % msg, flush=True))
+        bad = SR.refused(out)
+        if bad:
+            raise SystemExit("G21 %s: fd_error exceeds %.0e of the row's largest magnitude in (parameter, row) %s - not written"
+                             % (name, SR.FD_CAP, bad))
+        np.savez_compressed(os.path.join(GOLD, "g21_sensitivity_%s.npz" % name), state=out["state"], rows=out["rows"],
+                            values=out["values"], delta=out["delta"], D=out["D"], fd_error=out["fd_error"])
+        if os.path.exists(path):
+            with open(path) as fh:
+                meta["cases"] = json.load(fh)["cases"]
+        mag = np.max(np.abs(out["D"]), axis=2)
+        rel = np.where(mag > 0, out["fd_error"]/np.where(mag > 0, mag, 1.0), 0.0)
+        meta["cases"][name] = dict(SR.CASES[name], labels=[SR.label(p) for p in SR.CASES[name]["parameters"]],
+                                   values=[float(v) for v in out["values"]], delta=[float(v) for v in out["delta"]],
+                                   residual=float(out["residual"]), fd_error_relative=float(rel.max()))
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+        print("G21 %s written (%.0f s): steps %s, worst fd_error / max|row| %.2e, worst max|f| %.2e"
+              % (name, time.time() - t0, out["delta"], rel.max(), out["residual"]), flush=True)
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1550,6 +1594,8 @@ def main(argv):
             g_campaign(what.split("=", 1)[1] if "=" in what else None)
         elif what == "policy" or what.startswith("policy="):
             g_policy(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "sensitivity" or what.startswith("sensitivity="):
+            g_sensitivity(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

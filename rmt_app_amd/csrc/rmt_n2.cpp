@@ -444,6 +444,15 @@ static int launch(rmt_n2_handle* h, hipFunction_t f, void** args, int grid = -1,
     return 0;
 }
 
+// one reactor per lane, one wave per workgroup: the N1 kernel and the per-lane marches (kernels/71 .. 73)
+static int launch_lanes(rmt_n2_handle* h, hipFunction_t f, void** args) {
+    HIP_OK(hipEventRecord(h->ev0, h->stream));
+    HIP_OK(hipModuleLaunchKernel(f, (unsigned)((h->E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    HIP_OK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return 0;
+}
+
 extern "C" int rmt_n2_last_geometry(rmt_n2_handle* h, int* chunks, int* teams) {
     if (!h || !chunks || !teams) return fail("null argument");
     *chunks = h->last_chunks;
@@ -761,11 +770,7 @@ extern "C" int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* ou
     long long ms = (long long)max_steps;
     void* args[] = {(void*)&h->d_members1, (void*)&out, (void*)&E, (void*)&nout, (void*)&rtol, (void*)&atol,
                     (void*)&h0, (void*)&ms, (void*)&stats, (void*)&h->d_flags};
-    HIP_OK(hipEventRecord(h->ev0, h->stream));
-    HIP_OK(hipModuleLaunchKernel(h->f_n1, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-    HIP_OK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    return launch_lanes(h, h->f_n1, args);
 }
 
 extern "C" int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, int64_t max_iter, rmt_n2_stats* stats) {
@@ -779,12 +784,7 @@ extern "C" int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, in
     long long mi = (long long)max_iter;
     void* args[] = {(void*)&y_out, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
                     (void*)&h->d_flags};
-    // one reactor per lane, one wave per workgroup (the shape of rmt_n1_ros4)
-    HIP_OK(hipEventRecord(h->ev0, h->stream));
-    HIP_OK(hipModuleLaunchKernel(h->f_march, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-    HIP_OK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    return launch_lanes(h, h->f_march, args);
 }
 
 // solver-config "sensitivity" (kernels/73_sensitivity.inc): the tangent march over the converged state, behind
@@ -813,12 +813,7 @@ extern "C" int rmt_n2_steady_sens(rmt_n2_handle* h, const void* y, int n_params,
     int N = h->N, E = h->E;
     void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&n_params, (void*)&desc, (void*)&out,
                     (void*)&h->d_flags};
-    // one reactor per lane, one wave per workgroup (the shape of rmt_n2_steady_march)
-    HIP_OK(hipEventRecord(h->ev0, h->stream));
-    HIP_OK(hipModuleLaunchKernel(h->f_sens, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-    HIP_OK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    return launch_lanes(h, h->f_sens, args);
 }
 
 // ---------------------------------------------------------------------------------------------- campaign
@@ -871,11 +866,7 @@ extern "C" int rmt_n2_campaign_step(rmt_n2_handle* h, void* y, double dt, double
     long long mi = (long long)max_iter;
     void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
                     (void*)&h->d_flags, (void*)&h->d_profile, (void*)&h->d_law, (void*)&dt, (void*)&log_row};
-    HIP_OK(hipEventRecord(h->ev0, h->stream));
-    HIP_OK(hipModuleLaunchKernel(h->f_campaign, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-    HIP_OK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    return launch_lanes(h, h->f_campaign, args);
 }
 
 extern "C" int rmt_n2_get_profile(rmt_n2_handle* h, double* table_host) {
@@ -947,11 +938,7 @@ extern "C" int rmt_n2_campaign_policy_step(rmt_n2_handle* h, void* y, double dt,
     void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
                     (void*)&h->d_flags, (void*)&h->d_profile, (void*)&h->d_law, (void*)&dt, (void*)&log_row,
                     (void*)&h->d_policy, (void*)&levels, (void*)&policy_row, (void*)&comp, (void*)&max_evaluations};
-    HIP_OK(hipEventRecord(h->ev0, h->stream));
-    HIP_OK(hipModuleLaunchKernel(h->f_policy, (unsigned)((E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-    HIP_OK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    return launch_lanes(h, h->f_policy, args);
 }
 
 extern "C" int rmt_n2_get_campaign_level(rmt_n2_handle* h, double* levels_host) {

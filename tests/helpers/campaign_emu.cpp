@@ -13,20 +13,7 @@
 //                                            "state y_0 .. y_(V*N-1)"    y[v][z] row-major
 //                                          and stops at the first launch that fails
 //   "U a T dt"                             one call of rmt_campaign_update with the law: prints "upd value"
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#define RMT_HOST_EMULATION 1
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#ifndef INFINITY
-#define INFINITY __builtin_inf()
-#endif
-using std::trunc;
-#include RMT_GENERATED_SOURCE
+#include "rmt_host_unit.h"
 
 #if !RMT_CAMPAIGN
 #error "generate the source with RMT_CAMPAIGN"

@@ -16,20 +16,7 @@
 //                                            "state y_0 .. y_(V*N-1)"    y[v][z] row-major, the last march
 //                                          and stops at the first launch that fails (fail: the node solver's bits, or 64 =
 //                                          the bracket collapsed, 128 = the evaluation limit)
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#define RMT_HOST_EMULATION 1
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#ifndef INFINITY
-#define INFINITY __builtin_inf()
-#endif
-using std::trunc;
-#include RMT_GENERATED_SOURCE
+#include "rmt_host_unit.h"
 
 #if !RMT_CAMPAIGN || !RMT_CAMPAIGN_POLICY
 #error "generate the source with RMT_CAMPAIGN and RMT_CAMPAIGN_POLICY"

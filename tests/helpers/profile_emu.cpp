@@ -9,20 +9,7 @@
 //                                     differences under the same table: prints "jan" and "jfd", N*V*V numbers each
 //   "R tol max_iter"                  (march units) the steady-state march with the table: the output of
 //                                     steady_march_emu.cpp's record R
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#define RMT_HOST_EMULATION 1
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#ifndef INFINITY
-#define INFINITY __builtin_inf()
-#endif
-using std::trunc;
-#include RMT_GENERATED_SOURCE
+#include "rmt_host_unit.h"
 
 #if !RMT_PROFILE
 #error "generate the source with RMT_PROFILE"

@@ -17,20 +17,7 @@
 //                                         the sweep: prints "out" NP*(V+1)*N numbers ([p][v][z], row V = dP_z/dp) and
 //                                         "end failed_node" (-1: none)
 // Numbers are printed as hexadecimal floats.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#define RMT_HOST_EMULATION 1
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#ifndef INFINITY
-#define INFINITY __builtin_inf()
-#endif
-using std::trunc;
-#include RMT_GENERATED_SOURCE
+#include "rmt_host_unit.h"
 
 #if !RMT_SENS
 #error "generate the source with RMT_SENS (n2.sens_plan)"

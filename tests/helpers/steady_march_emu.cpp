@@ -9,20 +9,7 @@
 //   "Z P tol max_iter up_0 .. up_(V-1)"   ONE node started from its upstream state; prints
 //                                   "node 0 fail iters rejected nonfinite res" and "state y_0 .. y_(V-1)"
 // Numbers are printed as hexadecimal floats.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#define RMT_HOST_EMULATION 1
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#ifndef INFINITY
-#define INFINITY __builtin_inf()
-#endif
-using std::trunc;
-#include RMT_GENERATED_SOURCE
+#include "rmt_host_unit.h"
 
 #if !RMT_WITH_MARCH
 #error "generate the source with RMT_WITH_MARCH"

@@ -20,6 +20,7 @@ import pytest
 import torch  # noqa: F401  (before the library: the hipRTC that compiles is the one torch bundles)
 
 import campaign_ref as CR
+from helpers.host_build import build_helper
 import inputs as INP
 from oracle import n2_oracle as O
 from rmt_app_amd import campaign, hipbind, initial, n2, plan, profile, rmtExe
@@ -247,14 +248,7 @@ def _build(tmp, name, sanitize=False):
     src, _ = n2.plan_unit(mech, False, n2.campaign_plan(mech, zNo, row))
     tag = "%s%s%s" % (case["input"], "_iso" if mech.iso else "", "_san" if sanitize else "")
     if tag not in _BUILT:
-        unit = os.path.join(tmp, "unit_%s.inc" % tag)
-        with open(unit, "w") as f:
-            f.write(src)
-        exe = os.path.join(tmp, "campaign_%s" % tag)
-        san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off"] + san +
-                       ["-DRMT_GENERATED_SOURCE=\"%s\"" % unit, HELPER, "-o", exe], check=True, capture_output=True)
-        _BUILT[tag] = exe
+        _BUILT[tag] = build_helper(HELPER, src, tmp, tag, "campaign_%s" % tag, sanitize)
     return _BUILT[tag], mi, mech, named, row
 
 

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import inputs as INP
+from helpers.host_build import build_helper
 import sens_ref as SR
 from rmt_app_amd import n2, plan, rmtExe, sensitivity
 
@@ -113,12 +114,7 @@ def test_device_buffer_against_the_host_emulation_of_the_same_unit(tmp_path):
     assert not np.any(flags)
     mech, N = sens.mech, 20
     src, _ = n2.plan_unit(mech, False, n2.sens_plan(mech, N, sens.NP, None, rows))
-    unit = os.path.join(str(tmp_path), "unit.inc")
-    with open(unit, "w") as f:
-        f.write(src)
-    exe = os.path.join(str(tmp_path), "sens_emu")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DRMT_GENERATED_SOURCE=\"%s\"" % unit, HELPER,
-                    "-o", exe], check=True, capture_output=True)
+    exe = build_helper(HELPER, src, str(tmp_path), "sk", "sens_emu")
     kinds, idx = sens.descriptors(mech)
     hexes = lambda v: " ".join(float(x).hex() for x in np.ravel(v))
     text = "M %s\nS %d %s %s\n" % (hexes(rows[0]), N, " ".join("%d %d" % (k, i) for k, i in zip(kinds, idx)), hexes(y[0]))

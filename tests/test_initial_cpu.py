@@ -15,6 +15,7 @@ import pytest
 import torch  # noqa: F401  (before the library: the hipRTC that compiles is the one torch bundles)
 
 import inputs as INP
+from helpers.host_build import build_helper
 from oracle import n2_oracle as O
 from rmt_app_amd import hipbind, initial, n2, plan, rmtExe
 
@@ -142,13 +143,7 @@ HELPER = os.path.join(ROOT, "tests", "helpers", "steady_march_emu.cpp")
 def _build(tmp, name, zNo=20, sanitize=False):
     mi, mech, row = _rows(name, zNo)
     src, _ = n2.plan_unit(mech, False, n2.march_plan(mech, zNo, None, row))
-    unit = os.path.join(tmp, "unit_%s.inc" % name)
-    with open(unit, "w") as f:
-        f.write(src)
-    exe = os.path.join(tmp, "march_%s%s" % (name, "_san" if sanitize else ""))
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off"] + san +
-                   ["-DRMT_GENERATED_SOURCE=\"%s\"" % unit, HELPER, "-o", exe], check=True, capture_output=True)
+    exe = build_helper(HELPER, src, tmp, name, "march_%s%s" % (name, "_san" if sanitize else ""), sanitize)
     return exe, mi, mech, row
 
 

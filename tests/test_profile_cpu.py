@@ -17,6 +17,7 @@ import pytest
 import torch  # noqa: F401  (before the library: the hipRTC that compiles is the one torch bundles)
 
 import inputs as INP
+from helpers.host_build import build_helper
 import profile_ref as PR
 from oracle import n2_oracle as O
 from oracle.hostemu import HostEmu
@@ -282,13 +283,8 @@ def _build(tmp, name, zNo, feature):
     cp = n2.march_plan(mech, zNo, d, row) if feature == "march" else \
         n2.code_plan(mech, zNo, block=64, npt=1, rows=row, specialize=False, defines=d, features=(feature,))
     src, _ = n2.plan_unit(mech, False, cp)
-    unit = os.path.join(tmp, "unit_%s_%s.inc" % (name, feature))
-    with open(unit, "w") as f:
-        f.write(src)
-    exe = os.path.join(tmp, "profile_%s_%s" % (name, feature))
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DRMT_GENERATED_SOURCE=\"%s\"" % unit, HELPER,
-                    "-o", exe], check=True, capture_output=True)
-    return exe, mi, mech, row, src
+    tag = "%s_%s" % (name, feature)
+    return build_helper(HELPER, src, tmp, tag, "profile_" + tag), mi, mech, row, src
 
 
 def _run(exe, text):

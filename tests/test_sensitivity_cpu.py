@@ -23,6 +23,7 @@ import torch  # noqa: F401  (before the library: the hipRTC that compiles is the
 import inputs as INP
 import profile_ref as PR
 import sens_ref as SR
+from helpers.host_build import build_helper
 from rmt_app_amd import hipbind, isa, n2, plan, rmtExe, sensitivity
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -178,14 +179,7 @@ def _build(tmp, name, NP, params=(), profiled=False, zNo=20, sanitize=False):
         mi, mech, row = _rows(name, zNo, params)
         src, _ = n2.plan_unit(mech, False, n2.sens_plan(mech, zNo, NP, {"RMT_PROFILE": "1"} if profiled else None, row))
         tag = "%s_%d_%d%s%s" % (name, NP, len(params), "_p" if profiled else "", "_san" if sanitize else "")
-        unit = os.path.join(tmp, "unit_%s.inc" % tag)
-        with open(unit, "w") as f:
-            f.write(src)
-        exe = os.path.join(tmp, "sens_%s" % tag)
-        san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off"] + san +
-                       ["-DRMT_GENERATED_SOURCE=\"%s\"" % unit, HELPER, "-o", exe], check=True, capture_output=True)
-        _BUILT[key] = exe
+        _BUILT[key] = build_helper(HELPER, src, tmp, tag, "sens_%s" % tag, sanitize)
     mi, mech, row = _rows(name, zNo, params)
     return _BUILT[key], mi, mech, row
 

@@ -35,7 +35,7 @@
                  "tolerance": 1e-10, "max-evaluations": 40}                                 # absolute, on x_c; marches per step >= 4
   moves the common coolant level T (the member's MeTe; the zones of an "axial-profile" keep their offsets) in every step
   so that r(T) = x_c,outlet(T) - target = 0, inside ONE launch of rmt_n2_campaign_policy_step (the policy unit,
-  n2.campaign_policy_plan; a run without the key loads the unit it always did and returns the same bits).  Every value of
+  codeplan.campaign_policy_plan; a run without the key loads the unit it always did and returns the same bits).  Every value of
   r is a whole march.  The scheme, which `policy_emulate` below restates: march at lo and at hi; without a sign change
   the limit with the smaller |r| is accepted (a tie: lo) and the step is "saturated"; else one march at the carried level
   (step 0: MeTe clipped to the limits, then the previous step's accepted level) shrinks the bracket and Illinois regula

@@ -15,7 +15,7 @@
   the analytic node Jacobian.  "tolerance" bounds the scaled node residual max_i |f_i| / (F1 (zNo-1) max(|y_i|, 1e-6)) AND
   the last relative update of every node (a node whose residual stays above it at the noise of its own evaluation ends
   after three updates in a row within the bound); "max-iterations" the pseudo-time steps per node.
-* A member whose march does not converge raises (n2.flag_error: RMT_N2_FLAG_STEP / RMT_N2_FLAG_NONFINITE, the message
+* A member whose march does not converge raises (device.flag_error: RMT_N2_FLAG_STEP / RMT_N2_FLAG_NONFINITE, the message
   names the member and the node).  There is no fallback to the cold start.
 * On a coarse mesh a node may have several steady states.  The march follows the branch reached by relaxing from the
   upstream state.

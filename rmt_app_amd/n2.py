@@ -6,1028 +6,23 @@ The reference calls scipy's solve_ivp once per output interval with a Python RHS
 (fixed-step RK4 or adaptive Dormand-Prince RK45) over all mesh nodes of all ensemble members.
 torch is used only as the owner of device memory and streams.
 """
-import ctypes as C
 from collections import namedtuple
 from timeit import default_timer as timer
-
-import os
 
 import numpy as np
 
 from . import campaign, control, hipbind, initial, launches, monitor, plan, profile, schedule, sensitivity
+# (the two lists below are also the re-exports: every public name of codeplan and device stays importable from here)
+from .codeplan import (  # noqa: F401
+    FEATURE_DEFINES, KC_MAX_AGE, KC_REFRESH, MARCH_BLOCK, MAX_CHUNKS, N_CUS, CodePlan, campaign_plan, campaign_policy_plan,
+    choose_geometry, code_plan, code_plans, compile_mechanism, compile_options, compile_plan, device_arch, device_source,
+    forced_literals, forced_mode, forced_tail, forcing_level, is_campaign, is_forced, is_profiled, kc_period, kcache_choice,
+    march_plan, plan_unit, precompile, rk45_block, rk45_geometry, ros4_block, ros4_quad, sens_plan)
+from .device import FLAG_PRESSURE, AutoStepper, N2Device, flag_error, step_counts, stepper_args  # noqa: F401
 from .ensemble import DistributedEnsemble, active_ranks, guarded
-from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
 
-FLAG_PRESSURE = 32
 DEVICE_IVPS = ("hip-rk4", "hip-rk45", "hip-ros4", "hip-auto", "AM", "hip-ab3")
-FEATURE_DEFINES = {"ros4": "RMT_WITH_ROS4", "n1": "RMT_WITH_N1", "march": "RMT_WITH_MARCH"}
-MARCH_BLOCK = 64         # csrc/kernels/71_steady_march.inc: one reactor per lane, one wave per workgroup
-
-
-N_CUS = 256          # MI355X; the C library clamps the team count to the device's real CU count
-
-
-def choose_geometry(N, V, fp32=False, E=None):
-    """(block, nodes_per_thread) of the generated kernels for E reactors of N nodes.
-    The on-chip stepper holds block*npt nodes per workgroup; longer reactors are chained over
-    several workgroups (rmt_n2_rk4_chain).  The table is what measured fastest on MI355X
-    (profiles/round1_chain.md, round2_shapes.md):
-      * big ensembles: 512 threads x 2 nodes (1024-node chunks, 2 waves/SIMD);
-      * ensembles that would leave at least half of the 256 CUs idle with one workgroup per 1024 nodes:
-        the reactors are cut into 128-, 256- or 512-node chunks (the smallest that keeps E x chunks <= 256
-        workgroups, all resident), e.g. ONE 4096-node reactor over 32 CUs (10.7 us/step vs 217 us on one CU),
-        64 x 1024 nodes as 4 chunks each (1.55x the one-CU-per-reactor rate)."""
-    if N > 256 and E is not None and 2*E*(-(-N//1024)) <= N_CUS:
-        for block, npt in ((128, 1), (256, 1), (256, 2)):
-            if E*(-(-N//(block*npt))) <= N_CUS:
-                return block, npt
-    for block in (64, 128, 256, 512):
-        if N <= block:
-            return block, 1
-    return (512, 2) if V <= 8 else (512, 1)
-
-
-def ros4_quad(mech, fp32=False):
-    """True when the stiff stepper runs in its one-node-on-four-lanes layout (kernels/61_ros4_quad.inc): mechanisms
-    wider than 8 variables, whose V x V node inverse does not fit one lane's registers (model N2, fp64)."""
-    return mech.V > 8 and getattr(mech, "model", "N2") == "N2" and not fp32
-
-
-def ros4_block(V, N, fp32=False, quad=None):
-    """Workgroup size for the stiff stepper: at most 256 threads (one V x V block inverse per lane),
-    and the block's five stage vectors G_1..G_5 must fit in LDS next to the 16 KiB exp table and the
-    hand-over buffers (5*V*block*sizeof(real) <= 140 KiB).  (Quad layout, V > 8 in fp64: 256 threads = 64 nodes.)"""
-    if quad is None:
-        quad = V > 8 and not fp32
-    if quad:
-        return 256 if N > 32 else 64*((4*N + 63)//64)
-    block = min(256, 64*((N + 63)//64))
-    while block > 64 and 5*V*block*(4 if fp32 else 8) > 140*1024:
-        block //= 2
-    return block
-
-
-def rk45_block(V, N, fp32=False):
-    """Workgroup size for the adaptive explicit stepper: the largest (<= 256) whose seven stage
-    derivatives of a node block fit in LDS (7*V*block*sizeof(real) <= 112 KiB, csrc RMT_RK45_KLDS)."""
-    block = min(256, 64*((N + 63)//64))
-    while block > 64 and 7*V*block*(4 if fp32 else 8) > 112*1024:
-        block //= 2
-    return block
-
-
-MAX_CHUNKS = 64          # include/rmt_n2.h RMT_N2_MAX_CHUNKS
-
-
-def rk45_geometry(V, N, fp32=False, chain=True, E=None):
-    """(block, nodes_per_thread, defines) for the adaptive explicit stepper.  The on-chip kernels keep 4
-    long-lived vectors per node, RMT_RK45_LDS of them in LDS (V*block*npt reals each, at most 136 KiB
-    together), the rest in VGPRs - measured on MI355X (profiles/round2_rk45.md): 512 x 2 with 2 vectors in LDS
-    for V <= 8, 256 x 2 for the 12-species mechanism.  A reactor that fits one such workgroup runs
-    rmt_n2_rk45_reg; a longer one is cut into chunks of that size on as many CUs (rmt_n2_rk45_chain; `chain`),
-    up to MAX_CHUNKS; beyond that the memory-resident kernel (rk45_block).
-    `E` (reactors on this GPU, when the caller knows it): an ensemble that leaves CUs idle with those chunks is cut
-    finer - ONE node per lane, chunks of 512 / 256 nodes (256 / 128 for V > 8) - as long as all chunks of all
-    reactors stay co-resident: a step is latency-bound per lane, so half the work per lane on twice the CUs is
-    30-70 % faster (profiles/round2_rk45_chain.md)."""
-    size = 4 if fp32 else 8
-    big = V <= 8
-    if big and N <= 1024:
-        block, npt = choose_geometry(N, V, fp32)
-    elif N <= 512:
-        block, npt = (256, 2) if N > 256 else (64*((N + 63)//64), 1)
-    elif chain and -(-N//(1024 if big else 512)) <= min(MAX_CHUNKS, N_CUS):
-        block, npt = (512, 2) if big else (256, 2)
-    else:
-        return rk45_block(V, N, fp32), 1, {}
-    if chain and E is not None and N > 256:
-        for blk in ((256, 512) if big else (128, 256)):          # finest first
-            C = -(-N//blk)
-            if C >= 2 and blk < block*npt and E*C <= N_CUS and C <= MAX_CHUNKS:
-                block, npt = blk, 1
-                break
-    slots = 2
-    while slots > 0 and slots*V*block*npt*size > 136*1024:
-        slots -= 1
-    if slots == 0:
-        return rk45_block(V, N, fp32), 1, {}
-    return block, npt, {"RMT_RK45_LDS": str(slots)}
-
-
-KC_REFRESH = 8          # csrc/kernels/50_rk4.inc RMT_KC_REFRESH: the cache's reference point moves every 8th step ...
-KC_MAX_AGE = 1.3e-5     # ... RMT_KC_MAX_AGE: or sooner, so that no reference point is older than this much model time [s]
-
-
-def is_forced(defines):
-    """True for the prelude defines of a code object that evaluates a schedule (csrc/kernels/11_forcing.inc): its member
-    rows carry schedule.TAIL more doubles ("1") or schedule.TAIL + S more ("2": the schedule also moves the feed
-    composition) and none of the forced fields is baked into the kernel."""
-    return forcing_level(defines) in ("1", "2")
-
-
-def forcing_level(defines):
-    """The RMT_FORCING value of the prelude defines as a string: "0" (none), "1" or "2"."""
-    return str((defines or {}).get("RMT_FORCING", "0"))
-
-
-def forced_tail(defines, S):
-    """doubles a member row of that code object carries behind the ordinary 16 + S + NU"""
-    level = forcing_level(defines)
-    return schedule.TAIL + int(S) if level == "2" else schedule.TAIL if level == "1" else 0
-
-
-def is_profiled(defines):
-    """True for the prelude defines of a code object that reads an axial profile (csrc/kernels/12_profile.inc): its handle
-    needs the table of rmt_n2_set_profile, and it holds no chained kernel."""
-    return str((defines or {}).get(profile.DEFINE, "0")) == "1"
-
-
-def forced_literals(member_defines, level="1"):
-    """The sweep-invariant member fields a FORCED code object may take as literals: all but the ones the schedule moves -
-    three for RMT_FORCING 1, the inlet composition as well for RMT_FORCING 2 (``level``) - no RMT_MC_* literal may freeze a
-    forced field; the others never change between the launches of a run."""
-    moved = ("RMT_MC_THETA_IN", "RMT_MC_P0", "RMT_MC_TM") + (("RMT_MC_CIN",) if str(level) == "2" else ())
-    return {k: v for k, v in member_defines.items() if k not in moved}
-
-
-def forced_mode(ivp, N, block, npt, want=None, key="schedule", what="forcing"):
-    """The kernel form of a forced launch, set by the HOST (rmt_n2_set_mode): the chained forms do not carry the forcing,
-    so the library's auto mode must not pick them.  The same rule serves profiled runs (``key`` "axial-profile", ``what``
-    "profile"), forced or not.  "reg" (the on-chip steppers) when the reactor fits one workgroup,
-    else "mem"; the stiff stepper always runs rmt_n2_ros4_mem (any N on one workgroup).  `want`: solver-config
-    "device-mode"."""
-    if want not in (None, "auto", "reg", "mem"):
-        raise ValueError("solver-config 'device-mode' must be 'reg' or 'mem' together with '%s' (got %r): the "
-                         "chained kernels do not carry the %s" % (key, want, what))
-    if ivp == "hip-ros4":
-        return "mem"
-    fits = int(N) <= int(block)*int(npt)
-    if want == "reg" and not fits:
-        raise ValueError("solver-config 'device-mode': 'reg' holds at most %d nodes per reactor (zNo = %d)"
-                         % (int(block)*int(npt), int(N)))
-    return want if want in ("reg", "mem") else ("reg" if fits else "mem")
-
-
-def kc_period(defines, dt):
-    """steps between two moves of the reference point of a caching one-workgroup RK4 stepper at step size dt (the kernel's
-    own rule, csrc/kernels/50_rk4.inc rmt_rk4_reg_body)."""
-    K = int(defines.get("RMT_KC_REFRESH", 1))
-    age = float(defines.get("RMT_KC_MAX_AGE", KC_MAX_AGE))
-    return 1 if K <= 1 or not dt > 0 else int(min(float(K), max(1.0, age/dt)))
-
-
-def kcache_choice(mech, N, fp32, block, npt, lds_state, defines):
-    """(defines, lds_state) with the RK4 steppers' cache of the temperature-only rate constants switched on where it has
-    been measured to pay (csrc/kernels/50_rk4.inc rmt_rk4_reg_body / rmt_rk4_chain_body; profiles/round3_kcache.md), model
-    N2 in fp64 (the list is for at most 8 variables per node; wider mechanisms: see the table in the body):
-
-    * one workgroup per reactor at 512 x 2 (RMT_KCACHE; the bench shape, 1.62e10 -> 1.95e10 node-steps/s) and at the
-      small geometries of short reactors (2048 x 20 nodes at 64 x 1: 3.2e9 -> 5.0e9, 2048 x 128 at 128 x 1: 1.21e10 ->
-      1.53e10, 1024 x 256 at 256 x 1: 1.47e10 -> 1.58e10; profiles/round3_kcache.md): 1/T_ref,
-      log T_ref, T_ref, the Arrhenius constants AND the equilibrium constants (RMT_KCACHE_GEN 2: one slot each, the
-      exponent's change from the differences of its basis functions T^n, log T) when the mechanism's exponents decompose
-      that way and every table-driven exp is then a cached constant (the kernel keeps the 64-entry exp table, which makes
-      the room in LDS); else without the equilibrium constants (RMT_KCACHE_GEN 0).  y_n moves to LDS (lds_state 1) to make
-      room in the register file; the reference point moves every 8th step;
-    * chained workgroups, every geometry (RMT_KCACHE_CHAIN, RMT_KCACHE_GEN 0): 256 x 4096 nodes at 512 x 2 +10 %, 128 x
-      1024 at 256 x 2 +8 %, 64 x 1024 at 256 x 1 +5 %, ONE 4096-node reactor at 128 x 1 +7.5 %.
-
-    An explicit "RMT_KCACHE" / "RMT_KCACHE_CHAIN" in `defines` (0 or 1) is left alone, and so is an lds_state that does
-    not leave the room."""
-    defs = dict(defines or {})
-    chained = int(N) > int(block)*int(npt)
-    if is_forced(defs) and (chained or os.environ.get("RMT_N2_FORCED_PLAIN")):
-        return defs, lds_state       # (a forced reactor beyond one workgroup runs the memory-resident form, never the chain)
-    if is_profiled(defs) and (chained or os.environ.get("RMT_N2_PROFILED_PLAIN")):
-        return defs, lds_state       # (the same for a profiled one: a profiled unit has no chained kernel)
-    key = "RMT_KCACHE_CHAIN" if chained else "RMT_KCACHE"
-    geo = (int(block), int(npt))
-    model = getattr(mech, "model", "N2")
-    if key in defs or fp32 or model not in ("N2", "M2"):
-        return defs, lds_state
-    if model == "M2":
-        # the dimensional model: its one-workgroup stepper at 512 x 2 (which keeps y_n in LDS anyway), Arrhenius constants
-        # only - with the equilibrium constants its step loop spills (28 scratch accesses)
-        if chained or geo != (512, 2) or lds_state not in (None, 1) or mech.V > 8 \
-                or not mech.kcache_fits(fp32, block, npt, 1, gen=False):
-            return defs, lds_state
-        defs.update({key: "1", "RMT_KCACHE_GEN": "0"})
-        defs.setdefault("RMT_KC_REFRESH", str(KC_REFRESH))
-        return defs, 1
-    # where the cache measured faster (profiles/round3_kcache.md) -> the lds_state it needs (None: the geometry's default).
-    # At most 8 variables per node (DME): every chained geometry; one workgroup per reactor at 512 x 2, at 64 / 128 / 256
-    # threads and at 512 x 1 with y_n in LDS (1.52e10 -> 1.72e10; with the geometry's own lds_state it is SLOWER).  Wider mechanisms (12 species, V = 13): 64 x 1 (8.7e9 ->
-    # 1.21e10), 512 x 1 (1.07e10 -> 1.16e10) and the chained 512 x 1 (9.9e9 -> 1.04e10), with y_n in LDS; 128 x 1 is
-    # SLOWER there (8.8e9 -> 7.1e9).
-    if mech.V <= 8:
-        good = {geo: (1 if geo == (512, 2) else lds_state)} if chained and geo[1] <= 2 else \
-            {(512, 2): 1, (64, 1): lds_state, (128, 1): lds_state, (256, 1): lds_state, (512, 1): 1}
-    else:
-        good = {(512, 1): 1} if chained else {(64, 1): lds_state, (512, 1): 1}
-    if geo not in good or (good[geo] == 1 and lds_state not in (None, 1)):
-        return defs, lds_state
-    want = good[geo]
-    if chained:
-        if not mech.kcache_fits_chain(fp32, block, npt, want, gen=False):
-            return defs, lds_state
-        defs.update({key: "1", "RMT_KCACHE_GEN": "0"})
-        return defs, want
-    # equilibrium constants too where that measured faster: everywhere but at 128 x 1 (1.53e10 with the Arrhenius
-    # constants alone against 1.39e10 - the wider kernel loses a wave of occupancy there) and 512 x 1 (1.72e10 against 1.52e10)
-    if geo not in ((128, 1), (512, 1)) and mech.kcache_small_exp("basis") and mech.kcache_slots("basis") > mech.kcache_slots(False) \
-            and mech.kcache_fits(fp32, block, npt, want, gen="basis", small_exp=True, node_major=True):
-        # (a node's slots side by side in LDS: one address register per node; with slot-major rows of 8 KiB the far slots
-        # need registers of their own and the 512 x 2 step loop spills - 1.86e10 against 1.95e10 node-steps/s)
-        defs.update({key: "1", "RMT_KCACHE_GEN": "2", "RMT_KC_SMALL_EXP": "1", "RMT_KC_NODE_MAJOR": "1"})
-    elif mech.kcache_fits(fp32, block, npt, want, gen=False):
-        defs.update({key: "1", "RMT_KCACHE_GEN": "0"})
-    else:
-        return defs, lds_state
-    defs.setdefault("RMT_KC_REFRESH", str(KC_REFRESH))
-    return defs, want
-
-
-CodePlan = namedtuple("CodePlan", "block npt lds_state defines features")
-
-
-def code_plan(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),
-              rows=None, specialize=None, literals=None, newton=True):
-    """WHICH code object a run loads - the one place that decides it: geometry (the caller's, else choose_geometry for E
-    members per GPU), the RK4 rate-constant cache (kcache_choice), the optional kernel families, the stiff stepper's
-    layout, model M2's Newton sweeps and the sweep-invariant member fields as literals.  The single-process route passes
-    its member ``rows`` (E and, with ``specialize``, the literals come from them; a single reactor is NOT specialised by
-    default - every new operating point would cost a 2-3 s JIT); a multi-rank job passes the members per GPU and the
-    defines its ranks agreed on (``literals``).  A forced code object takes no literal for a field its schedule moves.
-    The translation unit and its cache key (plan_unit) and the hipRTC options (compile_options) follow from the record;
-    needs no GPU."""
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.float64)
-        rows = rows.reshape(1, -1) if rows.ndim == 1 else rows
-        E = rows.shape[0] if E is None else E
-        specialize = E >= 2 if specialize is None else specialize
-    b, n = choose_geometry(int(N), mech.V, fp32, E)
-    block, npt = int(block or b), int(npt or n)
-    defs, lds_state = kcache_choice(mech, N, fp32, block, npt, lds_state, defines)
-    # optional kernel families: "ros4" (stiff stepper), "n1" (steady-state model); their
-    # unrolled VxV linear algebra is most of the JIT time, so they are compiled on demand
-    for f in features:
-        defs[FEATURE_DEFINES[f]] = "1"
-    # the cross-wave part of the pressure scan (csrc/kernels/25_prefix.inc): the batched form where it was timed - the unit
-    # of the caching one-workgroup RK4 stepper of model N2 at 512 x 2, built for nothing else (the bench unit; the same
-    # condition as compile_options' register-pressure trackers).  The RK45 unit of that geometry, units with an optional
-    # kernel family and every other geometry keep the template's default, the scalar loop (profiles/prefix_chain.md)
-    if "RMT_PREFIX_MODE" not in defs and str(defs.get("RMT_KCACHE", "0")) == "1" and (block, npt) == (512, 2) \
-            and not features and "RMT_RK45_LDS" not in defs and not fp32 and getattr(mech, "model", "N2") == "N2":
-        defs["RMT_PREFIX_MODE"] = "4"
-    if "ros4" in features and "RMT_ROS_QUAD" not in defs and ros4_quad(mech, fp32) and npt == 1:
-        defs["RMT_ROS_QUAD"] = "1"            # wide mechanism: one node on four lanes (N2Device tells the C library)
-    if getattr(mech, "model", "N2") == "M2" and "RMT_M2_NEWTON" not in defs and rows is not None and newton:
-        # (a multi-rank job passes the maximum over its ranks as a define)
-        defs["RMT_M2_NEWTON"] = str(plan.m2_newton_sweeps(rows, mech, int(N)))
-    if specialize:                            # sweep-invariant member fields become literals (frees SGPRs)
-        literals = plan.uniform_member_defines(rows[:, :mech.row_width], mech.S)
-    if literals:
-        defs.update(forced_literals(literals, forcing_level(defs)) if is_forced(defs) else literals)
-    # "RMT_KCACHE": "1" (kcache_choice above, or the caller's own): the on-chip RK4 stepper caches the temperature-only
-    # rate constants per node in LDS - that has to fit
-    gen = plan.KCACHE_GEN[str(defs.get("RMT_KCACHE_GEN", "1"))]
-    small = str(defs.get("RMT_KC_SMALL_EXP", "0")) == "1"
-    if small and not mech.kcache_small_exp(gen):
-        raise ValueError("RMT_KC_SMALL_EXP=1: the mechanism has table-driven exp evaluations that are not cached constants")
-    if str(defs.get("RMT_KCACHE_CHAIN", "0")) == "1" and not mech.kcache_fits_chain(
-            fp32, block, npt, lds_state, gen, small, str(defs.get("RMT_KC_NODE_MAJOR", "0")) == "1"):
-        raise ValueError("RMT_KCACHE_CHAIN=1: the cache of the temperature-only rate constants (%d doubles per node) does "
-                         "not fit beside the chunk's RK4 vectors (model N2, fp64)" % mech.kcache_slots(gen))
-    if str(defs.get("RMT_KCACHE", "0")) == "1" and not (
-            int(N) <= block*npt and mech.kcache_fits(fp32, block, npt, lds_state, gen, small,
-                                                     str(defs.get("RMT_KC_NODE_MAJOR", "0")) == "1")):
-        raise ValueError("RMT_KCACHE=1: the cache of the temperature-only rate constants (%d doubles per node) does not "
-                         "fit this geometry (needs the on-chip RK4 stepper with its vectors in registers, model N2, fp64)"
-                         % mech.kcache_slots())
-    return CodePlan(block, npt, lds_state, defs, tuple(features))
-
-
-def march_plan(mech, N, defines=None, rows=None):
-    """The code object of the steady-state march (solver-config "initial", csrc/kernels/71_steady_march.inc): a unit of
-    its own - the stepper's code object and its cache key are those of a run without the key.  block = 64 (one reactor per
-    lane), the family "march" (RMT_WITH_MARCH: the analytic node Jacobian without the stiff stepper's kernels), no
-    rate-constant cache, fp64.  Of the run's ``defines`` only the row layout travels (RMT_FORCING: the rows are the
-    stepper's); the member fields stay run-time values, so one object serves every operating point of a mechanism."""
-    defs = {"RMT_KCACHE": "0", "RMT_KCACHE_CHAIN": "0"}
-    if is_forced(defines):
-        defs["RMT_FORCING"] = forcing_level(defines)
-    if is_profiled(defines):          # (the march reads the table for the node it is solving)
-        defs[profile.DEFINE] = "1"
-    return code_plan(mech, N, False, None, MARCH_BLOCK, 1, None, defs, ("march",), rows, specialize=False)
-
-
-def is_campaign(defines):
-    """True for the prelude defines of the campaign unit (csrc/kernels/72_campaign.inc): the one unit generated from the
-    whole template text (plan.Mechanism.source cuts that file's text out of every other unit)."""
-    return str((defines or {}).get(campaign.DEFINE, "0")) == "1"
-
-
-def campaign_plan(mech, N, rows=None):
-    """The code object of a time-on-stream run (solver-config "deactivation", csrc/kernels/72_campaign.inc): the profiled
-    march unit (march_plan) plus RMT_CAMPAIGN - rmt_n2_campaign_step beside rmt_n2_steady_march.  The only unit such a run
-    loads; one object serves every operating point, law and mesh of a mechanism."""
-    cp = march_plan(mech, N, {profile.DEFINE: "1"}, rows)
-    return CodePlan(cp.block, cp.npt, cp.lds_state, {**cp.defines, campaign.DEFINE: "1"}, cp.features)
-
-
-def campaign_policy_plan(mech, N, rows=None):
-    """The code object of a time-on-stream run with a "policy" (campaign.POLICY_DEFINE): the campaign unit plus
-    RMT_CAMPAIGN_POLICY - rmt_n2_campaign_policy_step beside rmt_n2_campaign_step.  A campaign without the key keeps loading
-    the unit of campaign_plan."""
-    cp = campaign_plan(mech, N, rows)
-    return CodePlan(cp.block, cp.npt, cp.lds_state, {**cp.defines, campaign.POLICY_DEFINE: "1"}, cp.features)
-
-
-def sens_plan(mech, N, n_params, defines=None, rows=None):
-    """The code object of a run with solver-config "sensitivity" (csrc/kernels/73_sensitivity.inc): whatever march_plan
-    gives for the run (forced or profiled rows) plus RMT_SENS and RMT_SENS_NP - rmt_n2_steady_sens beside
-    rmt_n2_steady_march.  ``mech``: the mechanism of the sensitivity unit (the "rate-constant" parameters among its
-    per-reactor inputs).  It takes the place of the march unit on the march handle (N2Device.attach_march: where its
-    mechanism is the run's own; else it gets a handle of its own beside the plain march unit); every other unit of the
-    run is what it is without the key."""
-    cp = march_plan(mech, N, defines, rows)
-    return CodePlan(cp.block, cp.npt, cp.lds_state,
-                    {**cp.defines, sensitivity.DEFINE: "1", sensitivity.DEFINE_NP: str(int(n_params))}, cp.features)
-
-
-def code_plans(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),
-               rows=None, specialize=None, literals=None, newton=True):
-    """EVERY code object a run loads, as CodePlans: the stepper's (code_plan with the same arguments, the feature "march"
-    taken out) and, with the feature "march", the unit of the steady-state march behind it (march_plan)."""
-    step = tuple(f for f in features if f != "march")
-    plans = [code_plan(mech, N, fp32, E, block, npt, lds_state, defines, step, rows, specialize, literals, newton)]
-    if "march" in features:
-        plans.append(march_plan(mech, N, defines, rows))
-    return plans
-
-
-def plan_unit(mech, fp32, cp):
-    """(translation unit, cache key) of a CodePlan"""
-    tpl = hipbind.kernel_template()
-    # (the user's lds_state, possibly None, is what selects the per-kernel defaults)
-    return (mech.source(tpl, fp32, cp.block, cp.npt, cp.lds_state, cp.defines),
-            mech.digest(tpl, fp32, cp.block, cp.npt, cp.lds_state, cp.defines))
-
-
-def compile_plan(mech, fp32, cp, arch="gfx950", extra_opts=""):
-    """The code object of a CodePlan, from the in-tree cache or hipRTC (no GPU needed)."""
-    src, key = plan_unit(mech, fp32, cp)
-    return hipbind.compile_cached(src, key, arch, compile_options(cp.block, cp.npt, cp.features, extra_opts, cp.defines))
-
-
-def device_source(mech, members, N, fp32=False, block=None, npt=None, lds_state=None, defines=None,
-                  specialize=None, features=()):
-    """What N2Device compiles for (mechanism, member rows, mesh): (block, npt, prelude #defines, translation unit, cache
-    key)."""
-    cp = code_plan(mech, N, fp32, None, block, npt, lds_state, defines, features, members, specialize)
-    return (cp.block, cp.npt, cp.defines) + plan_unit(mech, fp32, cp)
-
-
-def compile_options(block, npt, features=(), extra_opts="", defines=None):
-    """hipRTC options beyond the library's own (csrc/rmt_n2.cpp rmt_n2_compile) for a code object of this geometry.  The
-    RK4 steppers at 512 x 2 - two waves per SIMD at the register limit - are scheduled with LLVM's AMDGPU register
-    pressure trackers (`-amdgpu-use-amdgpu-trackers=1`): bench 2.018e10 -> 2.045e10 node-steps/s, chained 256 x 4096
-    nodes 1.53e10 -> 1.58e10; the stiff stepper (-1.5 %) and the small chunks of ONE long reactor (-1.9 %) are SLOWER
-    with it, and so is the on-chip RK45 stepper on the bench sweep (6.90e9 -> 6.71e9; tools/microbench/exp_r3ae.sh,
-    rk45_ab.py): code objects with optional kernel families or built for RK45 (rk45_geometry's "RMT_RK45_LDS") keep the
-    default."""
-    auto = "-mllvm -amdgpu-use-amdgpu-trackers=1" if ((int(block), int(npt)) == (512, 2) and not features
-                                                       and "RMT_RK45_LDS" not in (defines or {})) else ""
-    if os.environ.get("RMT_N2_NO_TRACKERS"):          # (A/B measurements)
-        auto = ""
-    if not auto or "amdgpu-use-amdgpu-trackers" in (extra_opts or ""):
-        return extra_opts or ""
-    return ("%s %s" % (extra_opts, auto)).strip()
-
-
-def precompile(mech, members, N, arch="gfx950", extra_opts="", **kw):
-    """Cross-compile (hipRTC, no GPU needed) the code object N2Device(mech, members, N, **kw) will load and
-    leave it in the in-tree cache; returns its cache key."""
-    cp = code_plan(mech, N, rows=members, **kw)
-    compile_plan(mech, kw.get("fp32", False), cp, arch, extra_opts)
-    return plan_unit(mech, kw.get("fp32", False), cp)[1]
-
-
-def flag_error(flags):
-    """Device status words (one per reactor) -> the exception the reference's Python path raises inside the user lambdas
-    (SURVEY.md section 5 'Failure detection') for the first reactor that has one set; None when all are clear."""
-    bad = np.nonzero(flags)[0]
-    if len(bad) == 0:
-        return None
-    f = int(flags[bad[0]])
-    where = "reactor %d of %d (flags=0x%x)" % (bad[0], len(flags), f)
-    if f & FLAG_DOMAIN:
-        return ValueError("math domain error in " + where)
-    if f & FLAG_DIV0:
-        return ZeroDivisionError("float division by zero in " + where)
-    if f & FLAG_OVERFLOW:
-        return OverflowError("math range error in " + where)
-    if f & FLAG_STEP:
-        return RuntimeError("adaptive step control failed (step underflow / max steps) in " + where)
-    if f & FLAG_NONFINITE:
-        return FloatingPointError("state became NaN/Inf in " + where + " - step size too large?")
-    if f & FLAG_PRESSURE:
-        return RuntimeError("model M2: the Newton sweeps of the pressure march did not converge in "
-                            + where + " - pass defines={'RMT_M2_NEWTON': 4} (pressure drop > 15 % of P)")
-    if f & (campaign.FLAG_POLICY_BRACKET | campaign.FLAG_POLICY_EVALS):
-        return RuntimeError("the coolant policy of a time-on-stream step gave up (%s) in %s"
-                            % ("its bracket collapsed: the outlet jumps there" if f & campaign.FLAG_POLICY_BRACKET
-                               else "evaluation limit reached", where))
-    return RuntimeError("device error in " + where)
-
-
-def stepper_args(cfg, stepper, first, auto=False):
-    """(rtol, atol, h0, max_steps) of N2Device.rk45 / .ros4 ("rk45" / "ros4") from the solver-config.  The first launch
-    of a stepper starts every reactor at h0; later ones RESUME (h0 < 0): each reactor starts from the step its own
-    controller proposed at the end of the previous launch (stats.h_last).  ``auto``: the explicit pair under "hip-auto"
-    has tolerances of its own."""
-    tol = "auto-rk45" if auto and stepper == "rk45" else stepper
-    h0 = float(cfg.get('h0', DEVICE_DEFAULTS[stepper + '-h0']))
-    return (float(cfg.get('rtol', DEVICE_DEFAULTS[tol + '-rtol'])), float(cfg.get('atol', DEVICE_DEFAULTS[tol + '-atol'])),
-            h0 if first else -h0, int(cfg.get('max-steps', DEVICE_DEFAULTS['rk45-max-steps'])))
-
-
-def step_counts(raw):
-    """(accepted, rejected) per reactor from the adaptive steppers' counters [E][4] = {t_end, h_last, accepted, rejected}
-    (the two counts travel as the bit patterns of int64)"""
-    return raw[:, 2].copy().view(np.int64), raw[:, 3].copy().view(np.int64)
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        raise hipbind.RmtN2Error("no HIP device visible: the N2 integrator has no CPU fallback")
-    return torch
-
-
-class N2Device:
-    """One compiled mechanism + E packed member rows on one GPU."""
-    # launches, row updates (set_members_async) and copies of the counters tensor (_stats) are queued on one stream, and
-    # nothing between two launches needs the host: integrate_intervals may queue several launches at once
-    stream_ordered = True
-
-    def __init__(self, mech, members, N, fp32=False, block=None, npt=None, device=None,
-                 extra_opts="", lds_state=None, defines=None, code=None, specialize=None,
-                 features=(), profile=None):
-        """``profile``: the table [E][2][N] of an axial profile (profile.Profile.table: per member the catalyst activities,
-        then the coolant offsets).  The code object is generated with RMT_PROFILE and the table uploaded before anything
-        is launched.  (``defines={"RMT_PROFILE": "1"}`` alone creates the profiled device without a table: set_profile.)"""
-        torch = _torch()
-        if profile is not None:
-            defines = {**(defines or {}), "RMT_PROFILE": "1"}
-        self.torch = torch
-        self.mech, self.N, self.fp32 = mech, int(N), bool(fp32)
-        members = np.ascontiguousarray(members, dtype=np.float64)
-        if members.ndim == 1:
-            members = members.reshape(1, -1)
-        self.forced = is_forced(defines)
-        self.row_width = mech.row_width + forced_tail(defines, mech.S)
-        assert members.shape[1] == self.row_width, \
-            "member rows must hold 16 + S + NU doubles (+ 4 when forced, + 4 + S with a forced composition)"
-        self.E = members.shape[0]
-        self.members = members
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        cp = code_plan(mech, self.N, self.fp32, None, block, npt, lds_state, defines, features, members, specialize,
-                       newton=code is None)
-        self.block, self.npt, self.defines, self.features = cp.block, cp.npt, cp.defines, cp.features
-        self.lds_state = mech.lds_state(self.fp32, self.block, self.npt, cp.lds_state)
-        if code is None:      # an ensemble rank may receive rank 0's code object instead
-            code = compile_plan(mech, self.fp32, cp, device_arch(self.device), extra_opts)
-        self._code = C.create_string_buffer(code, len(code))
-        p = hipbind.Plan()
-        p.abi_version = hipbind.ABI_VERSION
-        p.n_species, p.n_reactions, p.n_vars = mech.S, mech.R, mech.V
-        p.n_nodes, p.n_members, p.fp32 = self.N, self.E, int(self.fp32)
-        p.block, p.nodes_per_thread = self.block, self.npt
-        p.n_user_params = self.row_width - plan.MEMBER_FIXED - mech.S       # (a forced row's tail travels as 4 or 4 + S more)
-        self.ros_quad = str(self.defines.get("RMT_ROS_QUAD", "0")) == "1"
-        p.ros4_nodes_per_block = self.block//4 if self.ros_quad else 0
-        self.profiled = is_profiled(self.defines)
-        p.profiled = int(self.profiled)
-        p.code_object = C.cast(self._code, C.c_void_p)
-        p.code_size = len(code)
-        p.members = members.ctypes.data_as(C.POINTER(C.c_double))
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            hipbind.check(hipbind.lib().rmt_n2_create(C.byref(p), C.byref(h)))
-        self.h = h
-        # node-function evaluations one Jacobian of the stiff stepper costs: the analytic Jacobian comes with the
-        # stage-1 evaluation (rates and their partials in ONE fused pass, rmt_node_jac) and is charged as one more;
-        # the forward-difference form (RMT_ROS_JAC_FD 1) costs V columns, +1 in model M2 for the upwind coupling
-        fd = str(self.defines.get("RMT_ROS_JAC_FD", "0")) == "1"
-        self.jacobian_evals = (mech.V + (1 if getattr(mech, "model", "N2") == "M2" else 0)) if fd else 1
-        self.dtype = torch.float32 if self.fp32 else torch.float64
-        self._stats = torch.zeros((self.E, 4), dtype=torch.float64, device=self.device)
-        self.march = None       # a second device of the same rows with the steady-state march (attach_march)
-        self.sens = None        # ... and a third with the sensitivity unit, where that needs a mechanism of its own
-        self.use_current_stream()
-        self.profile = None
-        if profile is not None:
-            try:
-                self.set_profile(profile)
-            except Exception:
-                self.close()
-                raise
-
-    # -- plumbing
-    def use_current_stream(self):
-        s = self.torch.cuda.current_stream(self.device).cuda_stream
-        hipbind.check(hipbind.lib().rmt_n2_set_stream(self.h, C.c_void_p(s)))
-        self._stream = s
-
-    def set_members(self, members):
-        """Replace the per-reactor constant rows (same E) without recompiling - e.g. the next
-        point of a sweep.  Not available when member fields were baked into the kernel as literals
-        (``specialize``): those fields would silently keep their old values."""
-        if any(k.startswith("RMT_MC_") for k in self.defines) and not self.forced:
-            # (a forced device only ever has its forced fields and the tail refreshed - those are never literals)
-            raise hipbind.RmtN2Error("this kernel was specialised on its member rows "
-                                     "(N2Device(..., specialize=False) keeps them run-time)")
-        members = np.ascontiguousarray(members, dtype=np.float64).reshape(self.E, -1)
-        assert members.shape[1] == self.row_width
-        self.members = members
-        hipbind.check(hipbind.lib().rmt_n2_set_members(self.h, members.ctypes.data_as(C.POINTER(C.c_double))))
-
-    def set_members_async(self, members):
-        """set_members queued on the current stream without waiting for it (between two queued launches: the rows of a
-        forced run are refreshed before every launch).  Returns the page-locked staging tensor, which the caller keeps
-        alive until the stream has passed the copy."""
-        members = np.ascontiguousarray(members, dtype=np.float64).reshape(self.E, self.row_width)
-        pinned = self.torch.empty(members.shape, dtype=self.torch.float64, pin_memory=True)
-        pinned.copy_(self.torch.from_numpy(members))
-        self.members = members
-        hipbind.check(hipbind.lib().rmt_n2_set_members_async(self.h, C.c_void_p(pinned.data_ptr())))
-        return pinned
-
-    def set_profile(self, table):
-        """Upload the axial profile [E][2][N] (rmt_n2_set_profile: one synchronous copy, before the first launch).  Only
-        for a device whose code object was generated with RMT_PROFILE."""
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        if table.shape != (self.E, 2, self.N):
-            raise hipbind.RmtN2Error("the profile table must be [E][2][N] = %r doubles (got %r)"
-                                     % ((self.E, 2, self.N), table.shape))
-        hipbind.check(hipbind.lib().rmt_n2_set_profile(self.h, table.ctypes.data_as(C.POINTER(C.c_double))))
-        self.profile = table
-        if self.march is not None:
-            self.march.set_profile(table)
-        if self.sens is not None:
-            self.sens.set_profile(table)
-
-    def get_members(self):
-        """The device rows as they are now [E][row_width] (synchronises the stream): what the last refresh uploaded and
-        the controller's kernel wrote since."""
-        out = np.zeros((self.E, self.row_width))
-        hipbind.check(hipbind.lib().rmt_n2_get_members(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
-        return out
-
-    def set_mode(self, mode):
-        hipbind.check(hipbind.lib().rmt_n2_set_mode(self.h, {"auto": 0, "reg": 1, "mem": 2, "chain": 3}[mode]))
-
-    def close(self):
-        if getattr(self, "_mon", None) is not None:
-            self._mon.close()
-            self._mon = None
-        if getattr(self, "march", None) is not None:
-            self.march.close()
-            self.march = None
-        if getattr(self, "sens", None) is not None:
-            self.sens.close()
-            self.sens = None
-        if getattr(self, "h", None):
-            hipbind.lib().rmt_n2_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def monitor(self, y, out, residual=False):
-        """Queue the row reductions of the state y on the device's stream: out (device double [E][V][5]) = per member
-        and variable {y[N-1], max, argmax, min, max|dy/dt|} - the last one only with ``residual`` (rmt_n2_rhs at y is
-        queued first), else 0.  Nothing is copied or synchronised.  The monitor object (mechanism-independent kernels,
-        csrc/monitor_kernels.inc) is created on first use."""
-        self._chk_state(y)
-        assert out.is_cuda and out.dtype == self.torch.float64 and out.is_contiguous()
-        assert out.numel() == self.E*self.mech.V*monitor.SLOTS, "monitor output must be [E][V][5] doubles"
-        if getattr(self, "_mon", None) is None:
-            with self.torch.cuda.device(self.device):
-                self._mon = hipbind.Monitor(device_arch(self.device))
-        dydt = self.rhs(y) if residual else None       # (stays allocated until the stream is past the reduce: torch's
-        #                                                 caching allocator hands memory out in stream order)
-        self._mon.reduce(self._stream, y.data_ptr(), dydt.data_ptr() if residual else 0, self.E, self.mech.V, self.N,
-                         self.fp32, out.data_ptr())
-
-    def control(self, y, loop, k=None):
-        """Queue the controller's kernel on the device's stream, behind the refresh of the member rows and ahead of the
-        next stepper launch (csrc/control_kernels.inc): sample ``k`` of the ControlLoop - measure on the state y, evaluate
-        the law, write slice k of the log and the manipulated field of this device's rows - or, with k = None, only
-        write the held value into the rows again.  Nothing is copied or synchronised."""
-        if not self.forced or self.fp32:
-            raise hipbind.RmtN2Error("the controller writes the rows of a forced fp64 code object (RMT_FORCING 1 or 2)")
-        if k is not None:
-            self._chk_state(y)
-        assert loop.E == self.E
-        loop.kernel.update(self.h, y.data_ptr() if k is not None else 0, self.mech.V, self.N, loop.params.data_ptr(),
-                           loop.setpoints[k].data_ptr() if k is not None else 0, loop.state.data_ptr(),
-                           loop.log[k].data_ptr() if k is not None else 0, self.mech.row_width, loop.field, k is None)
-
-    def to_device(self, y):
-        t = self.torch.as_tensor(np.ascontiguousarray(y), dtype=self.dtype)
-        return t.reshape(self.E, self.mech.V*self.N).contiguous().to(self.device)
-
-    def _chk_state(self, y):
-        assert y.is_cuda and y.dtype == self.dtype and y.is_contiguous()
-        assert y.numel() == self.E*self.mech.V*self.N, "state must be [E][V][N]"
-
-    # -- hot path entry points
-    def rhs(self, y, t=0.0):
-        self._chk_state(y)
-        out = self.torch.empty_like(y)
-        hipbind.check(hipbind.lib().rmt_n2_rhs(self.h, float(t), C.c_void_p(y.data_ptr()),
-                                               C.c_void_p(out.data_ptr())))
-        return out
-
-    def rk4(self, y, dt, nsteps, t0=0.0):
-        """In place: nsteps RK4 steps of size dt."""
-        self._chk_state(y)
-        hipbind.check(hipbind.lib().rmt_n2_rk4(self.h, C.c_void_p(y.data_ptr()), float(t0), float(dt),
-                                               int(nsteps)))
-
-    def multistep(self, y, dt, nsteps, method="PreCorr3", t0=0.0):
-        """In place: the reference's AdBash3 / PreCorr3 (odeSolver.py:43-102), nsteps >= 3."""
-        self._chk_state(y)
-        hipbind.check(hipbind.lib().rmt_n2_multistep(
-            self.h, C.c_void_p(y.data_ptr()), float(t0), float(dt), int(nsteps),
-            {"AdBash3": 0, "PreCorr3": 1}[method]))
-
-    def rk45(self, y, t0, t1, rtol, atol, h0, max_steps):
-        self._chk_state(y)
-        hipbind.check(hipbind.lib().rmt_n2_rk45(self.h, C.c_void_p(y.data_ptr()), float(t0), float(t1),
-                                                float(rtol), float(atol), float(h0), int(max_steps),
-                                                C.c_void_p(self._stats.data_ptr())))
-
-    def ros4(self, y, t0, t1, rtol, atol, h0, max_steps):
-        """In place: stiff integration (RODAS4, order 4(3)) from t0 to t1 with per-reactor step control
-        (needs a code object generated with features=("ros4",) and block <= 512; 256 is fastest)."""
-        self._chk_state(y)
-        if "ros4" not in self.features:
-            raise hipbind.RmtN2Error("create the device with features=('ros4',) to use the stiff stepper")
-        hipbind.check(hipbind.lib().rmt_n2_ros4(self.h, C.c_void_p(y.data_ptr()), float(t0), float(t1),
-                                                float(rtol), float(atol), float(h0), int(max_steps),
-                                                C.c_void_p(self._stats.data_ptr())))
-
-    def attach_march(self, sens=None):
-        """A second handle on the same member rows whose code object holds the steady-state march (march_plan): the
-        stepper's own code object stays what it is without it.  steady_march / march_result then go through it.
-        ``sens`` = (n_params, mechanism, rows) (solver-config "sensitivity"): with the run's own mechanism the handle's code
-        object is the sensitivity unit (sens_plan) - the march kernel in it is the march unit's text - and steady_sens goes
-        through it as well.  With another mechanism (a "rate-constant" the run keeps a literal is a per-reactor input
-        there, the rows are widened by it) the march stays on the plain march unit, so that the started state is the one
-        of the run without the key, and a third handle holds the sensitivity unit for steady_sens alone."""
-        if "march" not in self.features and self.march is None:
-            if self.fp32 or getattr(self.mech, "model", "N2") != "N2":
-                raise hipbind.RmtN2Error("the steady-state march is for model N2 in fp64")
-            if sens is None or sens[1] is not self.mech:
-                mech, rows, cp = self.mech, self.members, march_plan(self.mech, self.N, self.defines, self.members)
-            else:
-                n_params, mech, rows = sens
-                cp = sens_plan(mech, self.N, n_params, self.defines, rows)
-            self.march = N2Device(mech, rows, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
-                                  defines=cp.defines, specialize=False, features=cp.features, profile=self.profile)
-            if sens is not None and sens[1] is not self.mech:
-                n_params, mech, rows = sens
-                cp = sens_plan(mech, self.N, n_params, self.defines, rows)
-                self.sens = N2Device(mech, rows, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
-                                     defines=cp.defines, specialize=False, features=cp.features, profile=self.profile)
-        return self
-
-    def steady_sens(self, y, kinds, indices):
-        """Parametric sensitivities of the steady state y (rmt_n2_steady_sens, behind steady_march on the same handle):
-        returns the device tensor [E][NP][V+1][N] - per member and parameter d(scaled state)/d(row value) and, in row V,
-        dP/d(row value).  ``kinds`` / ``indices``: sensitivity.Sensitivity.descriptors.  Queued on the stream, nothing is
-        synchronised; status() reads the flags.  Needs a code object of sens_plan with RMT_SENS_NP = len(kinds)."""
-        if self.sens is not None:
-            return self.sens.steady_sens(y, kinds, indices)
-        if "march" not in self.features and self.march is not None:
-            return self.march.steady_sens(y, kinds, indices)
-        self._chk_state(y)
-        if str(self.defines.get(sensitivity.DEFINE, "0")) != "1" or int(self.defines[sensitivity.DEFINE_NP]) != len(kinds):
-            raise hipbind.RmtN2Error("steady_sens needs the sensitivity unit (sens_plan) with RMT_SENS_NP = %d" % len(kinds))
-        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
-        indices = np.ascontiguousarray(indices, dtype=np.int32)
-        assert kinds.shape == indices.shape and kinds.ndim == 1
-        out = self.torch.zeros((self.E, len(kinds), self.mech.V + 1, self.N), dtype=self.torch.float64, device=self.device)
-        hipbind.check(hipbind.lib().rmt_n2_steady_sens(self.h, C.c_void_p(y.data_ptr()), len(kinds),
-                                                       kinds.ctypes.data_as(C.POINTER(C.c_int)),
-                                                       indices.ctypes.data_as(C.POINTER(C.c_int)),
-                                                       C.c_void_p(out.data_ptr())))
-        return out
-
-    def sens_status(self):
-        """The status words of the handle steady_sens ran on, read and cleared (synchronises)."""
-        if self.sens is not None:
-            return self.sens.status()
-        if "march" not in self.features and self.march is not None:
-            return self.march.status()
-        return self.status()
-
-    def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
-        """In place: every member's state becomes the discrete steady state f(y) = 0 of its device rows (a forced row: its
-        values at the row's reference time), found by marching from the inlet with one V x V solve per node
-        (rmt_n2_steady_march).  Queued on the stream, nothing is synchronised; march_result reads what came of it.
-        Needs features=("march",), or attach_march()."""
-        self._chk_state(y)
-        if "march" not in self.features:
-            if self.march is None:
-                raise hipbind.RmtN2Error("create the device with features=('march',) or call attach_march() to use the "
-                                         "steady-state march")
-            return self.march.steady_march(y, tol, max_iter)
-        hipbind.check(hipbind.lib().rmt_n2_steady_march(self.h, C.c_void_p(y.data_ptr()), float(tol), int(max_iter),
-                                                        C.c_void_p(self._stats.data_ptr())))
-
-    def march_result(self):
-        """(stats, flags) of the last steady_march (synchronises): per member the worst node's scaled residual, the node
-        that failed (-1: none), the largest per-node step count and the number of nodes that needed a rejected step; the
-        status words, read and cleared."""
-        if "march" not in self.features and self.march is not None:
-            return self.march.march_result()
-        raw = self._stats.cpu().numpy()
-        its, damped = step_counts(raw)
-        return ({"scaled-residual": raw[:, 0].copy(), "failed-node": raw[:, 1].astype(np.int64), "iterations": its,
-                 "nodes-damped": damped}, self.status())
-
-    def set_campaign_law(self, law):
-        """Upload the deactivation law [E][5] = {k_ref, Ed, Tref, m, a_inf} (rmt_n2_set_campaign_law: one blocking copy).
-        Needs the campaign unit (campaign_plan) and a profile table."""
-        law = np.ascontiguousarray(law, dtype=np.float64)
-        if law.shape != (self.E, len(campaign.LAW_KEYS)):
-            raise hipbind.RmtN2Error("the law must be [E][5] = %r doubles (got %r)" % ((self.E, 5), law.shape))
-        hipbind.check(hipbind.lib().rmt_n2_set_campaign_law(self.h, law.ctypes.data_as(C.POINTER(C.c_double))))
-        self.law = law
-
-    def campaign_step(self, y, dt, log_row, stats=None, tol=initial.DEFAULTS["tolerance"],
-                      max_iter=initial.DEFAULTS["max-iterations"]):
-        """One step of a campaign (rmt_n2_campaign_step): y becomes every member's steady state for the activities in the
-        handle's table, which then move over ``dt`` seconds at the node temperatures of that state.  ``log_row``: device
-        doubles [E][V+6]; ``stats``: device doubles [E][4] (default: the device's own, march_result reads them).  Queued on
-        the stream, nothing is synchronised."""
-        self._chk_state(y)
-        stats = self._stats if stats is None else stats
-        for t, n in ((log_row, self.E*(self.mech.V + campaign.LOG_EXTRA)), (stats, self.E*4)):
-            assert t.is_cuda and t.dtype == self.torch.float64 and t.is_contiguous() and t.numel() == n, \
-                "campaign_step: the log row is [E][V+6], the stats [E][4] device doubles"
-        hipbind.check(hipbind.lib().rmt_n2_campaign_step(self.h, C.c_void_p(y.data_ptr()), float(dt), float(tol),
-                                                         int(max_iter), C.c_void_p(log_row.data_ptr()),
-                                                         C.c_void_p(stats.data_ptr())))
-
-    def set_campaign_policy(self, rows, component, levels):
-        """Upload the policy rows [E][4] = {target, lo, hi, tolerance}, the index of the held component and the levels
-        [E] step 0 carries in (rmt_n2_set_campaign_policy: one blocking copy).  Needs the policy unit
-        (campaign_policy_plan), a profile table and a law."""
-        rows = np.ascontiguousarray(rows, dtype=np.float64)
-        levels = np.ascontiguousarray(levels, dtype=np.float64)
-        if rows.shape != (self.E, campaign.POLICY_ROW) or levels.shape != (self.E,):
-            raise hipbind.RmtN2Error("the policy rows must be [E][4] = %r doubles and the levels [E] (got %r and %r)"
-                                     % ((self.E, 4), rows.shape, levels.shape))
-        hipbind.check(hipbind.lib().rmt_n2_set_campaign_policy(self.h, rows.ctypes.data_as(C.POINTER(C.c_double)),
-                                                               int(component), levels.ctypes.data_as(C.POINTER(C.c_double))))
-
-    def campaign_policy_step(self, y, dt, log_row, policy_row, stats=None, tol=initial.DEFAULTS["tolerance"],
-                             max_iter=initial.DEFAULTS["max-iterations"],
-                             max_evaluations=campaign.POLICY_DEFAULTS["max-evaluations"]):
-        """campaign_step with the coolant policy (rmt_n2_campaign_policy_step): y becomes every member's steady state at the
-        coolant level that holds the target (or at the better limit), the activities then move over ``dt`` seconds.
-        ``policy_row``: device doubles [E][4] = {level, held, marches, saturated}.  Queued on the stream, nothing is
-        synchronised."""
-        self._chk_state(y)
-        stats = self._stats if stats is None else stats
-        for t, n in ((log_row, self.E*(self.mech.V + campaign.LOG_EXTRA)), (policy_row, self.E*campaign.POLICY_LOG),
-                     (stats, self.E*4)):
-            assert t.is_cuda and t.dtype == self.torch.float64 and t.is_contiguous() and t.numel() == n, \
-                "campaign_policy_step: the log row is [E][V+6], the policy row [E][4], the stats [E][4] device doubles"
-        hipbind.check(hipbind.lib().rmt_n2_campaign_policy_step(
-            self.h, C.c_void_p(y.data_ptr()), float(dt), float(tol), int(max_iter), int(max_evaluations),
-            C.c_void_p(log_row.data_ptr()), C.c_void_p(policy_row.data_ptr()), C.c_void_p(stats.data_ptr())))
-
-    def get_campaign_level(self):
-        """The carried coolant levels [E] as they are now (rmt_n2_get_campaign_level; synchronises the stream)."""
-        out = np.zeros(self.E)
-        hipbind.check(hipbind.lib().rmt_n2_get_campaign_level(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
-        return out
-
-    def get_profile(self):
-        """The handle's table [E][2][N] as it is now (rmt_n2_get_profile; synchronises the stream): the activities the
-        campaign steps have written, and the coolant offsets."""
-        out = np.zeros((self.E, 2, self.N))
-        hipbind.check(hipbind.lib().rmt_n2_get_profile(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
-        return out
-
-    def n1_profile(self, rows1, nout, rtol, atol, h0, max_steps, V1=None):
-        """Steady-state model N1 (needs features=("n1",)): one profile per member row of ``rows1`` (layout M1_*),
-        sampled at z* = k/(nout-1); returns the host array [E][nout][S+2] (S+1 when iso-thermal).  A module generated
-        for another steady model (RMT_SS_MODEL, steady.py) passes its own number of unknowns V1."""
-        torch = self.torch
-        rows1 = np.ascontiguousarray(rows1, dtype=np.float64).reshape(self.E, self.mech.row_width)
-        if V1 is None:
-            V1 = self.mech.S + (1 if self.mech.iso else 2)
-        out = torch.zeros((self.E, int(nout), V1), dtype=torch.float64, device=self.device)
-        hipbind.check(hipbind.lib().rmt_n1_profile(
-            self.h, rows1.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(out.data_ptr()), int(nout),
-            float(rtol), float(atol), float(h0), int(max_steps), C.c_void_p(self._stats.data_ptr())))
-        return out.cpu().numpy()
-
-    def rk45_stats(self):
-        raw = self._stats.cpu().numpy()
-        acc, rej = step_counts(raw)
-        return {"t_end": raw[:, 0].copy(), "h_last": raw[:, 1].copy(), "accepted": acc, "rejected": rej}
-
-    def status(self):
-        flags = np.zeros(self.E, dtype=np.uint32)
-        hipbind.check(hipbind.lib().rmt_n2_status(self.h, flags.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return flags
-
-    def last_geometry(self):
-        """(workgroups per reactor, teams) of the last rk4 / rk45 / ros4 launch - what the library's auto mode chose."""
-        c, t = C.c_int(), C.c_int()
-        hipbind.check(hipbind.lib().rmt_n2_last_geometry(self.h, C.byref(c), C.byref(t)))
-        return c.value, t.value
-
-    def fallbacks(self):
-        """Reactor-launches the cached RK4 steppers handed to their plain twins so far (rmt_n2_fallbacks): a reactor whose
-        temperature left the range of its cached rate constants during a launch is integrated again in full."""
-        n = C.c_uint64()
-        hipbind.check(hipbind.lib().rmt_n2_fallbacks(self.h, C.byref(n)))
-        return int(n.value)
-
-    def last_kernel_ms(self):
-        ms = C.c_float()
-        hipbind.check(hipbind.lib().rmt_n2_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
-
-    def raise_on_flags(self):
-        err = flag_error(self.status())
-        if err is not None:
-            raise err
-
-
-class AutoStepper:
-    """ivp "hip-auto": the device counterpart of LSODA's automatic method switching (what the reference's default
-    `solve_ivp(..., method="LSODA")` does, pbHomoReactor.py:3576, 3609), decided per output interval and for the
-    whole ensemble at once:
-
-      * the first interval starts with a PROBE: at most `auto-probe-steps` Dormand-Prince steps.  If they reach
-        the end of the interval the problem is not stiff at this scale and the explicit pair carries on.
-      * otherwise the step size the controller settled on tells how many explicit steps the interval would cost
-        ((t1 - t0) / min h_last: the explicit pair sits at its stability limit ~3.3/|lambda| on a stiff problem).
-        Up to `auto-max-explicit-steps` the interval is redone with the explicit pair, beyond that the
-        Rosenbrock stepper takes over - for good (chemistry gets stiffer as the bed heats up, not milder).
-      * an explicit interval that exhausts its step budget is redone with the stiff stepper as well, and one that
-        needed more than `auto-max-explicit-steps` steps is the last explicit one.
-
-    Two devices (the on-chip RK45 geometry and the Rosenbrock kernel family) share the state tensor."""
-    stream_ordered = False                  # the host decides between two launches
-
-    def __init__(self, dev_rk45, dev_ros4):
-        """dev_ros4: the stiff device, or a zero-argument factory for it (single-process runs build - and JIT-
-        compile - the Rosenbrock kernel family only when the problem turns out to be stiff)."""
-        self.d45, self._dr = dev_rk45, dev_ros4
-        self.mode = None                    # None: undecided, "rk45", "ros4"
-        self.last = dev_rk45
-        self.rhs_evals = 0
-        self.choices = []
-        self.jacobian_evals = dev_rk45.jacobian_evals
-        self.prev_steps = 0
-        self._started = {"rk45": False, "ros4": False}
-
-    @property
-    def dr(self):
-        if callable(self._dr):
-            self._dr = self._dr()
-            if getattr(self, "_rows", None) is not None:
-                self._dr.set_members(self._rows)
-            if getattr(self, "_loop", None) is not None:      # (its rows came from the host: the held value again)
-                self._dr.control(None, self._loop)
-        return self._dr
-
-    def set_members(self, rows):
-        """the member rows of the next launch, for both devices (a forced run refreshes them before every launch)"""
-        self._rows = rows
-        self.d45.set_members(rows)
-        if not callable(self._dr):
-            self._dr.set_members(rows)
-
-    def to_device(self, y):
-        return self.d45.to_device(y)
-
-    def close(self):
-        self.d45.close()
-        if not callable(self._dr):
-            self._dr.close()
-
-    def rk45_stats(self):
-        return self.last.rk45_stats()
-
-    def attach_march(self, sens=None):
-        self.d45.attach_march(sens)
-        return self
-
-    def steady_sens(self, y, kinds, indices):
-        return self.d45.steady_sens(y, kinds, indices)
-
-    def sens_status(self):
-        return self.d45.sens_status()
-
-    def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
-        """the steady-state march on the rows of the explicit device (both devices hold the same rows)"""
-        self.d45.steady_march(y, tol, max_iter)
-
-    def march_result(self):
-        return self.d45.march_result()
-
-    def monitor(self, y, out, residual=False):
-        self.last.monitor(y, out, residual)
-
-    def control(self, y, loop, k=None):
-        """the controller's kernel for both devices: the explicit one takes the sample, the stiff one - once it exists -
-        has the held value written into its own rows"""
-        self._loop = loop
-        self.d45.control(y, loop, k)
-        if not callable(self._dr):
-            self._dr.control(y, loop, None)
-
-    def raise_on_flags(self):
-        self.last.raise_on_flags()
-
-    def last_geometry(self):
-        return self.last.last_geometry()
-
-    @property
-    def _stats(self):
-        return self.last._stats
-
-    def _run(self, which, y, t0, t1, cfg, max_steps):
-        dev = self.d45 if which == "rk45" else self.dr
-        rtol, atol, h0, _ = stepper_args(cfg, which, not self._started[which], auto=True)
-        self._started[which] = True
-        getattr(dev, which)(y, t0, t1, rtol, atol, h0, int(max_steps))
-        self.last = dev
-        return dev
-
-    def _explicit(self, y, t0, t1, cfg, budget):
-        """One explicit attempt; True when every reactor reached t1 (other failures are left for raise_on_flags)."""
-        dev = self._run("rk45", y, t0, t1, cfg, budget)
-        st = dev.rk45_stats()
-        tried = st["accepted"] + st["rejected"]
-        self.rhs_evals += int(np.sum(6*tried) + dev.E)
-        done = bool(np.all(st["t_end"] >= t1))
-        if not done:
-            err = flag_error(dev.status() & ~np.uint32(FLAG_STEP))       # read and clear: only the step budget may be set
-            if err is not None:             # a genuine failure
-                raise err
-        return done, st
-
-    def advance(self, y, t0, t1, cfg):
-        hard_max = stepper_args(cfg, "ros4", False)[3]
-        if self.mode != "ros4":
-            backup = y.clone()
-            if self.mode is None:
-                done, st = self._explicit(y, t0, t1, cfg, min(hard_max, DEVICE_DEFAULTS['auto-probe-steps']))
-                if done:
-                    self.mode = "rk45"
-                else:
-                    hmin = float(np.min(st["h_last"]))
-                    est = (t1 - t0)/max(hmin, 1e-300)
-                    y.copy_(backup)
-                    self._started["rk45"] = False
-                    self.mode = "rk45" if est <= DEVICE_DEFAULTS['auto-max-explicit-steps'] else "ros4"
-                    if self.mode == "rk45":
-                        done, st = self._explicit(y, t0, t1, cfg, min(hard_max, int(4*est) + 200))
-                        if not done:
-                            y.copy_(backup)
-                            self.mode = "ros4"
-            else:
-                done, st = self._explicit(y, t0, t1, cfg, min(hard_max, 4*self.prev_steps + 200))
-                if not done:
-                    y.copy_(backup)
-                    self.mode = "ros4"
-            if self.mode == "rk45":
-                self.prev_steps = int(np.max(st["accepted"] + st["rejected"]))
-                self.choices.append("rk45")
-                if self.prev_steps > DEVICE_DEFAULTS['auto-max-explicit-steps']:
-                    self.mode = "ros4"          # the interval just taken was too expensive explicitly: hand over
-                return
-        dev = self._run("ros4", y, t0, t1, cfg, hard_max)
-        st = dev.rk45_stats()
-        self.rhs_evals += int(np.sum((6 + dev.jacobian_evals)*(st["accepted"] + st["rejected"])))
-        self.choices.append("ros4")
 
 
 # --------------------------------------------------------------------------- result packing
@@ -1093,13 +88,6 @@ def _progress(i, total, quiet):
           end="\r" if i < total else "\n")
 
 
-def compile_mechanism(mech, N, fp32=False, block=None, npt=None, lds_state=None, defines=None,
-                      arch="gfx950", E=None, extra_opts="", features=()):
-    """Code object for (mechanism, mesh size, members per rank) - what ensemble rank 0 compiles
-    and broadcasts; pass the same E/block/npt/lds_state/defines/features to N2Device(code=...)."""
-    return compile_plan(mech, fp32, code_plan(mech, N, fp32, E, block, npt, lds_state, defines, features), arch, extra_opts)
-
-
 def resolve_ivp(ivp):
     """the reference's "default" is SciPy's LSODA (pbHomoReactor.py:3576) - Adams / BDF with AUTOMATIC
     stiffness detection: it maps to "hip-auto" (AutoStepper below: explicit Dormand-Prince while the problem is
@@ -1111,21 +99,6 @@ def resolve_ivp(ivp):
         raise ValueError("`ivp` must be one of %s, 'default' or a SciPy method name (got %r)"
                          % (DEVICE_IVPS, ivp))
     return ivp
-
-
-def device_arch(device=None):
-    """Architecture the JIT targets: that of ``device``; without one the current GPU's, gfx950 when none is visible
-    (cross-compile)."""
-    if device is not None:
-        import torch
-        return torch.cuda.get_device_properties(device).gcnArchName.split(":")[0]
-    try:
-        import torch
-        if torch.cuda.is_available():
-            return device_arch(torch.cuda.current_device())
-    except Exception:
-        pass
-    return "gfx950"
 
 
 def device_cls():
@@ -1178,12 +151,9 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
         extra = {} if prof is None else {"profile": prof.table()}
         dev = device_cls()(mech, rows, zNo, fp32=fp32, block=block, npt=npt, defines=defines, features=features, **extra)
         if forcing is not None:
-            forcing.fix_mode(dev, "hip-ros4" if "ros4" in features else "explicit")
+            forcing.fix_mode(dev, features)
         elif prof is not None:
-            prof.modes["ros4" if "ros4" in features else "explicit"] = mode = forced_mode(
-                "hip-ros4" if "ros4" in features else "explicit", zNo, dev.block, dev.npt, prof.want_mode,
-                "axial-profile", "profile")
-            dev.set_mode(mode)
+            fix_mode(dev, prof, zNo, features, "axial-profile", "profile")
         if march:
             try:
                 if sens is not None:
@@ -1215,7 +185,7 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     dev = guarded(sync, device_cls(), mech, rows, zNo, fp32=fp32, block=cp.block, npt=cp.npt, lds_state=cp.lds_state,
                   defines=cp.defines, specialize=False, code=ens.code, features=features)
     if forcing is not None:
-        guarded(sync, forcing.fix_mode, dev, "hip-ros4" if "ros4" in features else "explicit")
+        guarded(sync, forcing.fix_mode, dev, features)
     return dev, ens.named, ens.IV
 
 
@@ -1284,6 +254,15 @@ def outlet_only(cfg):
     return out == 'outlet'
 
 
+def fix_mode(dev, by, N, features, key="schedule", what="forcing"):
+    """Fix the kernel form of a forced or profiled device (forced_mode) and record it in ``by.modes``.  ``by``: the run's
+    Forcing or profile.Profile, whose ``want_mode`` is solver-config "device-mode"."""
+    stiff = "ros4" in features              # (all forced_mode tells apart: the stiff stepper always runs its "mem" form)
+    mode = forced_mode("hip-ros4" if stiff else "explicit", N, dev.block, dev.npt, by.want_mode, key, what)
+    dev.set_mode(mode)
+    by.modes["ros4" if stiff else "explicit"] = mode
+
+
 class Forcing:
     """A parsed schedule bound to one run: the local members' ordinary rows and the refresh of the device rows ahead of
     every launch of the run's list (schedule.Schedule.forced_rows)."""
@@ -1303,10 +282,8 @@ class Forcing:
             self.rows, self.named = np.array(rows, dtype=np.float64), list(named)
         return self.sched.forced_rows(self.rows, self.named, *self.first)
 
-    def fix_mode(self, dev, ivp):
-        mode = forced_mode(ivp, self.N, dev.block, dev.npt, self.want_mode)
-        dev.set_mode(mode)
-        self.modes["ros4" if ivp == "hip-ros4" else "explicit"] = mode
+    def fix_mode(self, dev, features):
+        fix_mode(dev, self, self.N, features)
 
     def refresh(self, dev, t0, t1, queued=False):
         """the rows of the launch (t0, t1) onto the device; ``queued`` (a stream-ordered device): between the queued
@@ -1488,6 +465,15 @@ def attach_monitor(raw, sync, convert):
     return [convert(e, raw[e]) for e in range(raw.shape[0])]
 
 
+def attach_entries(res, key, entries):
+    """The members' result entries of one solver-config key: the first member's under ``res[key]`` and, where the result
+    has an "ensemble" list, every member's under the same key of its own result."""
+    res[key] = entries[0]
+    if "ensemble" in res:
+        for member, entry in zip(res["ensemble"], entries):
+            member[key] = entry
+
+
 def steady_profiles(modelInput, members_inputs, pack, nout, defines=None, extra=None, handle_rows=None):
     """What the steady-state models (n1.run_n1, steady.run_steady) share: pack the members' rows (``pack(mi, mech)`` ->
     (named, row)), open an N2 handle of the module with the steady kernel family, ONE guarded launch of n1_profile, and
@@ -1664,15 +650,62 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
     res["device-stats"] = dstats
     if members_inputs:
         res["ensemble"] = [result(p, mi, zNo, cam.outputs) for p, mi in zip(packs, inputs)]
-    res[campaign.KEY] = entries[0]
+    attach_entries(res, campaign.KEY, entries)
     if prof is not None:
-        res["axial-profile"] = profile.result_entry(prof, 0)
-    if members_inputs:
-        for e, entry in enumerate(res["ensemble"]):
-            entry[campaign.KEY] = entries[e]
-            if prof is not None:
-                entry["axial-profile"] = profile.result_entry(prof, e)
+        attach_entries(res, "axial-profile", [profile.result_entry(prof, e) for e in range(E)])
     return res
+
+
+RunKeys = namedtuple("RunKeys", "sched ctl forced_by mon ini prof sens")
+
+
+def parse_keys(modelInput, members_inputs, ivp, tNo, E, V, ranked, with_schedule):
+    """The optional solver-config keys of a dynamic run, parsed and checked against their budgets; absent = None = exactly
+    the run without it.  ``ranked``: one rank of a multi-rank job; ``with_schedule``: the model takes more than "monitor".
+      sched  "schedule": time-varying inlet / coolant conditions (schedule.py)
+      ctl    "control": a sampled PI controller per member on the device (control.py).  A controlled run is a forced run:
+             without a "schedule" it gets a constant one of every member's own values - ``forced_by`` is what forces the run
+      mon    "monitor": time series between the output times (monitor.py)
+      ini    "initial": where the run starts (initial.py); None = the reference's cold start
+      prof   "axial-profile": catalyst activity and coolant zones along the bed (profile.py); knows the "device-mode"
+      sens   "sensitivity": parametric sensitivities of the steady state the run starts from (sensitivity.py)"""
+    sched = schedule.parse(modelInput, members_inputs, ivp) if with_schedule else None
+    control.check_model(modelInput)
+    ctl, forced_by = control.parse(modelInput, members_inputs, ivp, sched, ranked) if with_schedule else (None, sched)
+    if ctl is not None:
+        ctl.check_budget(PIPELINE_BYTES)
+    mon = monitor.parse(modelInput, tNo)
+    if mon is not None:
+        mon.check_budget(E, V, PIPELINE_BYTES)
+    ini = initial.parse(modelInput, ranked) if with_schedule else None
+    profile.check_model(modelInput)
+    prof = profile.parse(modelInput, members_inputs, ivp, ranked) if with_schedule else None
+    if prof is not None:
+        prof.want_mode = modelInput['solver-config'].get('device-mode')
+    sens = sensitivity.parse(modelInput, members_inputs, ranked) if with_schedule else None
+    return RunKeys(sched, ctl, forced_by, mon, ini, prof, sens)
+
+
+def run_geometry(ivp, mech, zNo, fp32, block, npt, defines, E_gpu, carried=()):
+    """(block, nodes per thread, prelude defines) of the stepper of `ivp`; an explicit ``block`` / ``npt`` of the solver-config
+    is left alone.  ``carried``: a (solver-config key, what it adds) pair for each of "schedule" and "axial-profile" the run
+    has: neither the stiff stepper's four-lane form nor the chained kernels carry the forcing or the profile."""
+    for key, what in carried:
+        if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
+            raise NotImplementedError("solver-config '%s' with the stiff stepper needs a mechanism of at most 8 "
+                                      "variables per node (this one has %d): its four-lane form does not carry the "
+                                      "%s - use ivp 'hip-rk45' or 'hip-rk4'" % (key, mech.V, what))
+    defines = dict(defines or {})
+    if block is not None:
+        return block, npt, defines
+    if ivp == "hip-rk4" and carried:          # the geometry of ONE workgroup per reactor (no chunks)
+        block, npt = choose_geometry(zNo, mech.V, fp32)
+    elif ivp == "hip-ros4":
+        block, npt = ros4_block(mech.V, zNo, fp32, ros4_quad(mech, fp32)), 1
+    elif ivp == "hip-rk45":
+        block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, **({"chain": False} if carried else {"E": E_gpu}))
+        defines.update(geo_defs)
+    return block, npt, defines
 
 
 def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result, fp32=False, defines=None,
@@ -1695,29 +728,8 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
     mech = mechanism_for(modelInput, inputs, cfg)
     sync = active_ranks(len(inputs)) if members_inputs else None       # one rank of a torchrun job?
     E_gpu = len(inputs) if sync is None else max(sync.counts)
-    block, npt = cfg.get('block'), cfg.get('nodes-per-thread')
-    # "schedule": time-varying inlet / coolant conditions (schedule.py); absent = None = exactly the run without it
-    sched = schedule.parse(modelInput, members_inputs, ivp) if with_schedule else None
-    # "control": a sampled PI controller per member on the device (control.py); absent = None = exactly the run without it.
-    # A controlled run is a forced run: without a "schedule" it gets a constant one of every member's own values.
-    control.check_model(modelInput)
-    ctl, forced_by = control.parse(modelInput, members_inputs, ivp, sched, sync is not None) if with_schedule \
-        else (None, sched)
-    if ctl is not None:
-        ctl.check_budget(PIPELINE_BYTES)
-    # "monitor": time series between the output times (monitor.py); absent = None = exactly the run without it
-    mon = monitor.parse(modelInput, tNo)
-    if mon is not None:
-        mon.check_budget(len(inputs), mech.V, PIPELINE_BYTES)
-    # "initial": where the run starts (initial.py); absent = None = the reference's cold start, exactly the run without it
-    ini = initial.parse(modelInput, sync is not None) if with_schedule else None
-    # "axial-profile": catalyst activity and coolant zones along the bed (profile.py); absent = None = exactly the run
-    # without it
-    profile.check_model(modelInput)
-    prof = profile.parse(modelInput, members_inputs, ivp, sync is not None) if with_schedule else None
-    # "sensitivity": parametric sensitivities of the steady state the run starts from (sensitivity.py); absent = None =
-    # exactly the run without it
-    sens = sensitivity.parse(modelInput, members_inputs, sync is not None) if with_schedule else None
+    sched, ctl, forced_by, mon, ini, prof, sens = parse_keys(modelInput, members_inputs, ivp, tNo, len(inputs), mech.V,
+                                                             sync is not None, with_schedule)
     # the ONE launch list of the run; a sample that fell on a mark carries that mark's time from here on (result entries)
     walk, sample_times, control_times = launches.merge(
         opT, tNo, forced_by.times if forced_by is not None else (), mon.times if mon is not None else None,
@@ -1726,32 +738,14 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         mon.times = sample_times
     if ctl is not None:
         ctl.times = control_times
+    carried = ([("schedule", "forcing")] if forced_by is not None else []) \
+        + ([("axial-profile", "profile")] if prof is not None else [])
+    block, npt, defines = run_geometry(ivp, mech, zNo, fp32, cfg.get('block'), cfg.get('nodes-per-thread'), defines, E_gpu,
+                                       carried)
     forcing = None
     if forced_by is not None:
-        if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
-            raise NotImplementedError("solver-config 'schedule' with the stiff stepper needs a mechanism of at most 8 "
-                                      "variables per node (this one has %d): its four-lane form does not carry the "
-                                      "forcing - use ivp 'hip-rk45' or 'hip-rk4'" % mech.V)
         forcing = Forcing(forced_by if sync is None else forced_by.members(sync.lo, sync.hi), walk, zNo,
                           cfg.get('device-mode'))
-        if ivp == "hip-rk4" and block is None:
-            # the geometry of ONE workgroup per reactor (no chunks: the chained kernels do not carry the forcing)
-            block, npt = choose_geometry(zNo, mech.V, fp32)
-    if prof is not None:
-        if ivp in ("hip-ros4", "hip-auto") and ros4_quad(mech, fp32):
-            raise NotImplementedError("solver-config 'axial-profile' with the stiff stepper needs a mechanism of at most 8 "
-                                      "variables per node (this one has %d): its four-lane form does not carry the "
-                                      "profile - use ivp 'hip-rk45' or 'hip-rk4'" % mech.V)
-        prof.want_mode, prof.modes = cfg.get('device-mode'), {}
-        if ivp == "hip-rk4" and block is None:          # ONE workgroup per reactor, as for a forced run
-            block, npt = choose_geometry(zNo, mech.V, fp32)
-    if ivp == "hip-ros4" and block is None:
-        block, npt = ros4_block(mech.V, zNo, fp32, ros4_quad(mech, fp32)), 1
-    defines = dict(defines or {})
-    if ivp == "hip-rk45" and block is None:
-        block, npt, geo_defs = rk45_geometry(mech.V, zNo, fp32, **({"chain": False} if forcing is not None or prof is not None
-                                                                 else {"E": E_gpu}))
-        defines.update(geo_defs)
     if ivp == "hip-auto":
         dev, named_local, IV = open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block, npt, forcing=forcing,
                                          march=ini is not None, prof=prof, sens=sens)
@@ -1802,31 +796,15 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         # multi-rank: rank 0 holds the whole sweep, the other ranks None (and an empty dataPack)
         res["ensemble"] = [result(p, mi, zNo, opTSpan) for p, mi in zip(packs, inputs)] if packer else None
     if ctl is not None:
-        entries = [ctl.result_entry(logs[:, e]) for e in range(logs.shape[1])]
-        res["control"] = entries[0]
-        if members_inputs:
-            for entry, c in zip(res["ensemble"], entries):
-                entry["control"] = c
+        attach_entries(res, "control", [ctl.result_entry(logs[:, e]) for e in range(logs.shape[1])])
     if prof is not None:
-        res["axial-profile"] = profile.result_entry(prof, 0)
-        if members_inputs:
-            for e, entry in enumerate(res["ensemble"]):
-                entry["axial-profile"] = profile.result_entry(prof, e)
+        attach_entries(res, "axial-profile", [profile.result_entry(prof, e) for e in range(len(inputs))])
     if started is not None:
-        res["initial"] = started[0]
-        if members_inputs:
-            for entry, st in zip(res["ensemble"], started):
-                entry["initial"] = st
+        attach_entries(res, "initial", started)
     if sensed is not None:
-        res[sensitivity.KEY] = sensed[0]
-        if members_inputs:
-            for entry, se in zip(res["ensemble"], sensed):
-                entry[sensitivity.KEY] = se
+        attach_entries(res, sensitivity.KEY, sensed)
     if monitors:
-        res["monitor"] = monitors[0]
-        if members_inputs:
-            for entry, m in zip(res["ensemble"], monitors):
-                entry["monitor"] = m
+        attach_entries(res, "monitor", monitors)
     if sync is not None:
         res["ensemble-shard"] = {"rank": sync.rank, "world": sync.world, "members": [sync.lo, sync.hi]}
     if display and packer:

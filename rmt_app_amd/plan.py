@@ -305,7 +305,7 @@ class Mechanism:
         if "RMT_KINETICS_SOURCE" not in template:
             raise ValueError("kernel template lacks the RMT_KINETICS_SOURCE marker")
         # ... and the text of the sensitivity sweep (csrc/kernels/73_sensitivity.inc, between its two marks) into the
-        # sensitivity unit only (RMT_SENS, n2.sens_plan)
+        # sensitivity unit only (RMT_SENS, codeplan.sens_plan)
         sens = str((defines or {}).get("RMT_SENS", "0")) == "1"
         if not sens:
             if str((defines or {}).get("RMT_SENS_NP", "0")) != "0":

@@ -34,7 +34,7 @@ ACTIVITY, COOLANT = "catalyst-activity", "medium-temperature"
 KEYS = ("position", ACTIVITY, COOLANT)
 MODELS = ("N2",)
 DEFINE = "RMT_PROFILE"
-WIDE = 8                 # n2.ros4_quad: beyond this many variables per node the stiff stepper runs its four-lane layout
+WIDE = 8                 # codeplan.ros4_quad: beyond this many variables per node the stiff stepper runs its four-lane layout
 
 
 def check_model(modelInput):
@@ -77,7 +77,7 @@ class Profile:
         self.given = tuple(bool(g) for g in given)
         self.E, self.N = self.activity.shape
         self.z = node_positions(self.N)
-        # what the run records: solver-config "device-mode" and the kernel forms the host fixed (n2.open_members)
+        # what the run records: solver-config "device-mode" and the kernel forms the host fixed (n2.parse_keys, n2.fix_mode)
         self.want_mode, self.modes = None, {}
 
     def table(self):

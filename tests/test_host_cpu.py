@@ -955,3 +955,17 @@ def test_single_process_and_multi_rank_routes_load_the_same_code_object(case, mo
                     features=features, forcing=forcing())
     assert len(single) == 1 and len(asked) == 1 and single[0][0] == key
     assert asked[0] == single[0], (single, asked)
+
+
+def test_n2_re_exports_what_the_bench_and_the_build_import(monkeypatch):
+    """The code plans live in rmt_app_amd.codeplan and the ctypes handle in rmt_app_amd.device; every name bench.py and
+    build() import from rmt_app_amd.n2 is still there and is the same object, and the device class the run drivers
+    instantiate is looked up in n2's namespace at call time."""
+    from rmt_app_amd import codeplan, device, n2
+    for name in ("rk45_geometry", "ros4_block", "kc_period", "compile_mechanism", "precompile", "choose_geometry",
+                 "compile_plan", "march_plan", "code_plan", "campaign_plan", "campaign_policy_plan", "sens_plan"):
+        assert getattr(n2, name) is getattr(codeplan, name), name
+    assert n2.N2Device is device.N2Device
+    made = []
+    monkeypatch.setattr(n2, "N2Device", lambda: made.append(1) or "stand-in")
+    assert n2.device_cls()() == "stand-in" and made == [1]

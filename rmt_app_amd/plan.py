@@ -24,6 +24,7 @@ import re
 import numpy as np
 
 from . import compdb
+from .emit import Emission
 from .lowering import trace
 from .settings import MODEL_SETTING, PROCESS_SETTING
 
@@ -94,6 +95,17 @@ def wilke(visc, x, MW):
 # "0" evaluates them in full, "1" caches value and exponent (two slots), "2" caches the value and forms the exponent's
 # change from the differences of its basis functions T^n, log T (one slot; lowering.Lowered.kcache_plan)
 KCACHE_GEN = {"0": False, "1": True, "2": "basis"}
+
+
+# How Mechanism.source / node_kinetics read a switch among the prelude defines.  Each key keeps the test it always had
+# (values arrive as strings or numbers): some are on only as "1", some are on unless "0"; RMT_WITH_ROS4, RMT_WITH_N1,
+# RMT_WITH_MARCH and RMT_KINETICS_KTAB are plain truthiness (the string "0" is true there).
+def _is1(d, key):
+    return str(d.get(key, "0")) == "1"
+
+
+def _not0(d, key, default="1"):
+    return str(d.get(key, default)) != "0"
 
 
 class Mechanism:
@@ -306,13 +318,14 @@ class Mechanism:
             raise ValueError("kernel template lacks the RMT_KINETICS_SOURCE marker")
         # ... and the text of the sensitivity sweep (csrc/kernels/73_sensitivity.inc, between its two marks) into the
         # sensitivity unit only (RMT_SENS, codeplan.sens_plan)
-        sens = str((defines or {}).get("RMT_SENS", "0")) == "1"
+        d = defines or {}
+        sens = _is1(d, "RMT_SENS")
         if not sens:
-            if str((defines or {}).get("RMT_SENS_NP", "0")) != "0":
+            if _not0(d, "RMT_SENS_NP", "0"):
                 raise ValueError("RMT_SENS_NP: only together with RMT_SENS=1 (n2.sens_plan)")
             template = _cut(template, SENS_MARKS)
-        if str((defines or {}).get("RMT_CAMPAIGN", "0")) != "1":
-            if str((defines or {}).get("RMT_CAMPAIGN_POLICY", "0")) != "0":
+        if not _is1(d, "RMT_CAMPAIGN"):
+            if _not0(d, "RMT_CAMPAIGN_POLICY", "0"):
                 raise ValueError("RMT_CAMPAIGN_POLICY: only together with RMT_CAMPAIGN=1 (n2.campaign_policy_plan)")
             template = _cut(template, CAMPAIGN_MARKS)
         # one reciprocal for the independent divisions of the rate laws (lowering.Lowered.div_groups).  RMT_DIV_BATCH is
@@ -322,22 +335,18 @@ class Mechanism:
         # Not in fp32 either: v_rcp_f32 has no Newton step that would turn the reciprocal of an overflowed product into
         # NaN, it returns 0 and the rates would be finite and wrong - and the range is 1e+-38 there.  The same goes for
         # the plain 1.0/b of a kernel built with RMT_FAST_MATH 0.
-        with_jac = bool((defines or {}).get("RMT_WITH_ROS4") or (defines or {}).get("RMT_WITH_N1")
-                        or (defines or {}).get("RMT_WITH_MARCH"))
-        batch = str((defines or {}).get("RMT_DIV_BATCH", "1")) != "0" and not with_jac and not fp32 \
-            and str((defines or {}).get("RMT_FAST_MATH", "1")) != "0"
-        kin = self.device_dag().emit("rmt_kinetics", const_table=bool((defines or {}).get("RMT_KINETICS_KTAB")),
-                                     kcache=(str((defines or {}).get("RMT_KCACHE", "0")) == "1"
-                                             or str((defines or {}).get("RMT_KCACHE_CHAIN", "0")) == "1"),
-                                     kcache_gen=KCACHE_GEN[str((defines or {}).get("RMT_KCACHE_GEN", "1"))],
-                                     kcache_thr=(defines or {}).get("RMT_KCACHE_THR"),
-                                     div_batch=batch)
-        kin += self.node_kinetics(defines, fp32, with_jac)
-        if (defines or {}).get("RMT_WITH_ROS4") or (defines or {}).get("RMT_WITH_MARCH"):
+        with_jac = bool(d.get("RMT_WITH_ROS4") or d.get("RMT_WITH_N1") or d.get("RMT_WITH_MARCH"))
+        batch = _not0(d, "RMT_DIV_BATCH") and not with_jac and not fp32 and _not0(d, "RMT_FAST_MATH")
+        kin = self.device_dag().emit("rmt_kinetics", const_table=bool(d.get("RMT_KINETICS_KTAB")),
+                                     kcache=_is1(d, "RMT_KCACHE") or _is1(d, "RMT_KCACHE_CHAIN"),
+                                     kcache_gen=KCACHE_GEN[str(d.get("RMT_KCACHE_GEN", "1"))],
+                                     kcache_thr=d.get("RMT_KCACHE_THR"), div_batch=batch)
+        kin += self.node_kinetics(d, fp32, with_jac)
+        if d.get("RMT_WITH_ROS4") or d.get("RMT_WITH_MARCH"):
             # the node Jacobian of the stiff stepper and of the steady-state march is analytic: rates AND their partials
             # by T, x_i, C_i
             kin += self.device_dag().gradient().emit_jac("rmt_kinetics_jac")
-        if (defines or {}).get("RMT_WITH_N1"):
+        if d.get("RMT_WITH_N1"):
             # steady-state model N1: the pressure is a state variable, so the partials by P as well
             dag = self.device_dag()
             wrt = sorted({dag.g.nodes[i][1] for i in dag.live if dag.g.nodes[i][0] == "in"})
@@ -359,7 +368,7 @@ class Mechanism:
         each its own switch among the defines, default on ("0" switches it off; with all three off the unit has no such
         function and rmt_node_post calls rmt_kinetics as before):
 
-          RMT_KC_FOLD        literal prefactors inside the cached constants (lowering.Lowered.emit kcache_fold)
+          RMT_KC_FOLD        literal prefactors inside the cached constants (emit.Emission kcache_fold)
           RMT_KIN_FOLD_FM    the rates leave scaled by the member field FM = F1/GaMaCoTe0 (rate_scale; needs RMT_KC_FOLD):
                              a literal of the unit or, read at run time, multiplied in where the reference point moves
           RMT_KIN_GAIN_RCP   the reciprocal of the heat balance's gain joins the rate laws' division group (extra_den)
@@ -368,22 +377,18 @@ class Mechanism:
         Only callers with a cache use the function (rmt_node_post): the plain twin of a caching stepper keeps rmt_kinetics.
         Not in units that also print a gradient DAG, in fp32 or with RMT_FAST_MATH 0 (the rule of the division pass)."""
         d = defines or {}
-        on = lambda k: str(d.get(k, "1")) != "0"
-        cached = str(d.get("RMT_KCACHE", "0")) == "1" or str(d.get("RMT_KCACHE_CHAIN", "0")) == "1"
-        if not cached or with_jac or fp32 or not on("RMT_FAST_MATH") or self.model != "N2" or self.steady \
-                or d.get("RMT_KINETICS_KTAB"):
+        if not (_is1(d, "RMT_KCACHE") or _is1(d, "RMT_KCACHE_CHAIN")) or with_jac or fp32 or not _not0(d, "RMT_FAST_MATH") \
+                or self.model != "N2" or self.steady or d.get("RMT_KINETICS_KTAB"):
             return ""
-        fold, gain = on("RMT_KC_FOLD"), on("RMT_KIN_GAIN_RCP") and on("RMT_DIV_BATCH") and not self.iso
-        fm = fold and on("RMT_KIN_FOLD_FM")
+        fold, gain = _not0(d, "RMT_KC_FOLD"), _not0(d, "RMT_KIN_GAIN_RCP") and _not0(d, "RMT_DIV_BATCH") and not self.iso
         if not (fold or gain):
             return ""
-        dag = self.device_dag()
-        text = dag.emit("rmt_kinetics_node", const_table=bool(d.get("RMT_KINETICS_KTAB")), kcache=True,
-                        kcache_gen=KCACHE_GEN[str(d.get("RMT_KCACHE_GEN", "1"))], kcache_thr=d.get("RMT_KCACHE_THR"),
-                        div_batch=on("RMT_DIV_BATCH"), kcache_fold=fold, rate_scale=fm,
-                        extra_den=gain, head=False)
+        em = Emission(self.device_dag(), "rmt_kinetics_node", kcache=True,
+                      kcache_gen=KCACHE_GEN[str(d.get("RMT_KCACHE_GEN", "1"))], kcache_thr=d.get("RMT_KCACHE_THR"),
+                      div_batch=_not0(d, "RMT_DIV_BATCH"), kcache_fold=fold,
+                      rate_scale=fold and _not0(d, "RMT_KIN_FOLD_FM"), extra_den=gain, head=False)
         return ("#define RMT_KIN_NODE 1\n#define RMT_KIN_RATES_FM %d\n#define RMT_KIN_GAIN_DEN %d\n"
-                % (1 if dag.rates_scaled else 0, 1 if gain else 0)) + text
+                % (1 if em.rates_scaled else 0, 1 if gain else 0)) + em.text
 
     @property
     def row_width(self):

@@ -97,10 +97,7 @@ def _ancestors(dag, i):
     """every node the value of node i depends on (i itself not included)"""
     seen, stack = set(), [i]
     while stack:
-        op, a, b = dag.g.nodes[stack.pop()]
-        if op in ("const", "in"):
-            continue
-        for o in [a] + ([b] if (b is not None and op != "powi") else []):
+        for o in dag.g.operands(stack.pop()):
             if o not in seen:
                 seen.add(o)
                 stack.append(o)

@@ -335,6 +335,45 @@ int rmt_n2_get_members(rmt_n2_handle* h, double* members);
 int rmt_n2_control_update(rmt_n2_control* c, rmt_n2_handle* h, const double* y, int V, int N, const double* params,
                           const double* setpoint, double* state, double* log, int tail_at, int field, int hold);
 
+/* Fit (solver-config "fit"): kinetic parameter estimation from steady-state data - the reduction over the experiments and
+ * one Levenberg-Marquardt step on the device, between rmt_n2_steady_sens of one iteration and rmt_n2_steady_march of the
+ * next (csrc/fit_kernels.inc, a translation unit of its own, independent of any mechanism: compile rmt_n2_fit_source()
+ * with rmt_n2_compile and the option -ffp-contract=off - both kernels are then reproducible on the host - and load it with
+ * rmt_n2_fit_create on the current device).
+ * rmt_n2_fit_step enqueues TWO kernels on the stream of `h` and does not synchronise.  `h` is an N2 handle of the
+ * sensitivity unit (rmt_n2_steady_march and rmt_n2_steady_sens in one code object, fp64) whose members are the experiments
+ * and whose per-reactor inputs hold the fitted constants; S, V, N must be the handle's.
+ *   y         DEVICE [E][V][N] doubles, the marched state
+ *   sens      DEVICE [E][n_params][V+1][N] doubles as rmt_n2_steady_sens wrote it for the fitted columns (kind 4)
+ *   stats     DEVICE [E] the march's statistics: a member with h_last >= 0 (a failed node) counts as failed
+ *   columns   HOST n_params ints, 1 <= n_params <= 8: the user column of each fitted constant
+ *   meas      DEVICE [E][MQ][3] doubles {code, value, weight = 1/sigma}; code = a species index (outlet mole fraction), S
+ *             (outlet temperature, K), S+1 (peak temperature, K); entries with weight 0 are padding; 1 <= MQ <= 64
+ *   pred      DEVICE [E][MQ] doubles, receives the predictions (0 at a padded entry)
+ *   contrib   DEVICE [E][46] doubles, receives per experiment {C = 1/2 sum r^2, g = J^T r [8], the upper triangle of J^T J
+ *             row by row [36], failed (1.0: the march failed or a number is not finite)}, r = (pred - value) weight
+ *   state     DEVICE [80] doubles, zero before the first call: {started, C_cur, lambda, nu, converged, passes, status,
+ *             predicted reduction, p_cur[8], p_trial[8], g_cur[8], H_cur[36], delta[8], reserved[4]}
+ *   log_slice DEVICE [68] doubles, this call's slice of the caller's log: {C_trial, C_cur, lambda, nu, accepted, converged,
+ *             failed experiments, status, p_trial[8] (what the rows now hold), p_cur[8], g[8], H[36] (this pass's sums)}
+ * The kernel rmt_n2_fit_residuals_f64, one wave per experiment, writes pred and contrib; rmt_n2_fit_update_f64, one workgroup, sums
+ * the 46 columns over the experiments in index order - no atomics, the sums do not depend on the launch geometry - and
+ * evaluates the law: the first call sets the current point from the columns of member 0 (status 1 when an experiment
+ * failed there); a trial is accepted when its cost is finite, no experiment failed and it is below C_cur; on accept
+ * lambda <- lambda max(1/3, 1 - (2 rho - 1)^3), nu = 2 with rho = (C_cur - C_trial) / (1/2 delta^T (lambda D delta - g)), on
+ * reject lambda <- lambda nu, nu <- 2 nu; (H + lambda D) delta = -g by Cholesky, D = diag(H) floored at 1e-300, on a pivot
+ * that is not positive lambda <- 10 lambda at most 8 times, then status 2; converged when max_j |delta_j| / max(|p_j|, 1e-300)
+ * <= tolerance or C_cur == 0.  The trial values p_cur + delta are written into the columns 16 + S + columns[j] of EVERY
+ * member's device row.  Converged (or with a status): p_trial = p_cur and later calls change nothing but pred, contrib and
+ * their log slice. */
+const char* rmt_n2_fit_source(void);
+typedef struct rmt_n2_fit rmt_n2_fit;
+int rmt_n2_fit_create(const void* code, size_t size, rmt_n2_fit** out);
+void rmt_n2_fit_destroy(rmt_n2_fit* f);
+int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens, const rmt_n2_stats* stats, int S,
+                    int V, int N, int n_params, const int* columns, const double* meas, int MQ, double* contrib,
+                    double* pred, double* state, double* log_slice, double tolerance, double damping0);
+
 const char* rmt_n2_last_error(void);
 int rmt_n2_abi_version(void);
 

@@ -28,6 +28,10 @@ static const char* const k_monitor_source =
 static const char* const k_control_source =
 #include "control_kernels_embed.h"
     ;
+// the fit's translation unit (fit_kernels.inc): mechanism-independent, compiled on its own
+static const char* const k_fit_source =
+#include "fit_kernels_embed.h"
+    ;
 
 static thread_local std::string g_err;
 
@@ -1140,5 +1144,85 @@ extern "C" int rmt_n2_control_update(rmt_n2_control* c, rmt_n2_handle* h, const 
                     (void*)&width, (void*)&tail_at,    (void*)&field,  (void*)&hold};
     HIP_OK(hipModuleLaunchKernel(c->f_update, (unsigned)grid, 1, 1, RMT_N2_CONTROL_BLOCK, 1, 1, 0, h->stream, args,
                                  nullptr));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- fit
+// Kinetic parameter estimation (fit_kernels.inc): the residual kernel - one wave per experiment at 256 threads, at most
+// RMT_N2_FIT_MAX_GRID workgroups, the experiments beyond them walked grid-stride - and behind it the update kernel, ONE
+// workgroup of one wave, on the handle's stream.
+#define RMT_N2_FIT_BLOCK 256
+#define RMT_N2_FIT_MAX_GRID 64
+#define RMT_N2_FIT_MAX_PARAMS 8
+#define RMT_N2_FIT_MAX_QUANTITIES 64
+
+struct rmt_n2_fit : SideModule {
+    hipFunction_t f_residuals = nullptr, f_update = nullptr;
+};
+
+extern "C" const char* rmt_n2_fit_source(void) { return k_fit_source; }
+
+extern "C" void rmt_n2_fit_destroy(rmt_n2_fit* f) {
+    if (!f) return;
+    side_unload(f);
+    delete f;
+}
+
+extern "C" int rmt_n2_fit_create(const void* code, size_t size, rmt_n2_fit** out) {
+    if (!code || !size || !out) return fail("rmt_n2_fit_create: null argument");
+    *out = nullptr;
+    rmt_n2_fit* f = new rmt_n2_fit();
+    if (side_load(f, "rmt_n2_fit_create", "fit", code,
+                  {{"rmt_n2_fit_residuals_f64", &f->f_residuals}, {"rmt_n2_fit_update_f64", &f->f_update}})) {
+        delete f;
+        return 1;
+    }
+    *out = f;
+    return 0;
+}
+
+extern "C" int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens,
+                               const rmt_n2_stats* stats, int S, int V, int N, int n_params, const int* columns,
+                               const double* meas, int MQ, double* contrib, double* pred, double* state, double* log_slice,
+                               double tolerance, double damping0) {
+    if (!f || !h || !y || !sens || !stats || !columns || !meas || !contrib || !pred || !state || !log_slice)
+        return fail("rmt_n2_fit_step: null argument");
+    if (n_params < 1 || n_params > RMT_N2_FIT_MAX_PARAMS)
+        return fail("rmt_n2_fit_step: 1..8 parameters (got %d)", n_params);
+    if (!h->f_sens || !h->f_march)
+        return fail("rmt_n2_fit_step: this handle's code object is not the sensitivity unit (no rmt_n2_steady_sens beside "
+                    "rmt_n2_steady_march)");
+    if (h->fp32) return fail("rmt_n2_fit_step: fp64 handles only");
+    if (h->device != f->device)
+        return fail("rmt_n2_fit_step: the handle lives on device %d, the fit on %d", h->device, f->device);
+    if (S != h->S || V != h->V || N != h->N)
+        return fail("rmt_n2_fit_step: S=%d V=%d N=%d are not the handle's (%d, %d, %d)", S, V, N, h->S, h->V, h->N);
+    if (MQ < 1 || MQ > RMT_N2_FIT_MAX_QUANTITIES)
+        return fail("rmt_n2_fit_step: 1..%d measured quantities per experiment (got %d)", RMT_N2_FIT_MAX_QUANTITIES, MQ);
+    if (!(tolerance >= 0) || !(damping0 > 0)) return fail("rmt_n2_fit_step: tolerance >= 0 and damping > 0");
+    struct { int col[RMT_N2_FIT_MAX_PARAMS]; } cols;
+    std::memset(&cols, 0, sizeof(cols));
+    for (int j = 0; j < n_params; ++j) {
+        if (columns[j] < 0 || columns[j] >= h->NU)
+            return fail("rmt_n2_fit_step: parameter %d: user column %d is out of range (NU = %d)", j, columns[j], h->NU);
+        cols.col[j] = columns[j];
+    }
+    if (((size_t)y | (size_t)sens | (size_t)stats | (size_t)meas | (size_t)contrib | (size_t)pred | (size_t)state |
+         (size_t)log_slice) % sizeof(double))
+        return fail("rmt_n2_fit_step: misaligned pointer");
+    ON_DEVICE(h);
+    int E = h->E, width = RMT_N2_MEMBER_FIXED + h->S + h->NU;
+    const int waves = RMT_N2_FIT_BLOCK / 64;
+    int grid = (E + waves - 1) / waves;
+    if (grid > RMT_N2_FIT_MAX_GRID) grid = RMT_N2_FIT_MAX_GRID;
+    void* args1[] = {(void*)&y,    (void*)&sens,    (void*)&stats, (void*)&h->d_members, (void*)&meas,
+                     (void*)&pred, (void*)&contrib, (void*)&E,     (void*)&S,            (void*)&V,
+                     (void*)&N,    (void*)&n_params, (void*)&MQ,   (void*)&width};
+    HIP_OK(hipModuleLaunchKernel(f->f_residuals, (unsigned)grid, 1, 1, RMT_N2_FIT_BLOCK, 1, 1, 0, h->stream, args1,
+                                 nullptr));
+    void* args2[] = {(void*)&contrib, (void*)&h->d_members, (void*)&state,    (void*)&log_slice, (void*)&E,
+                     (void*)&S,       (void*)&n_params,     (void*)&width,    (void*)&cols,      (void*)&tolerance,
+                     (void*)&damping0};
+    HIP_OK(hipModuleLaunchKernel(f->f_update, 1, 1, 1, 64, 1, 1, 0, h->stream, args2, nullptr));
     return 0;
 }

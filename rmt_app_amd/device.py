@@ -318,23 +318,44 @@ class N2Device:
                                      defines=cp.defines, specialize=False, features=cp.features, profile=self.profile)
         return self
 
-    def steady_sens(self, y, kinds, indices):
+    def steady_sens(self, y, kinds, indices, out=None):
         """Parametric sensitivities of the steady state y (rmt_n2_steady_sens, behind steady_march on the same handle):
         returns the device tensor [E][NP][V+1][N] - per member and parameter d(scaled state)/d(row value) and, in row V,
         dP/d(row value).  ``kinds`` / ``indices``: sensitivity.Sensitivity.descriptors.  Queued on the stream, nothing is
-        synchronised; status() reads the flags.  Needs a code object of sens_plan with RMT_SENS_NP = len(kinds)."""
+        synchronised; status() reads the flags.  Needs a code object of sens_plan with RMT_SENS_NP = len(kinds).
+        ``out``: a device tensor of that shape to write into (default: a new one, zeroed)."""
         if self._sens_dev() is not self:
-            return self._sens_dev().steady_sens(y, kinds, indices)
+            return self._sens_dev().steady_sens(y, kinds, indices, out)
         self._chk_state(y)
         if str(self.defines.get(sensitivity.DEFINE, "0")) != "1" or int(self.defines[sensitivity.DEFINE_NP]) != len(kinds):
             raise hipbind.RmtN2Error("steady_sens needs the sensitivity unit (sens_plan) with RMT_SENS_NP = %d" % len(kinds))
         kinds = np.ascontiguousarray(kinds, dtype=np.int32)
         indices = np.ascontiguousarray(indices, dtype=np.int32)
         assert kinds.shape == indices.shape and kinds.ndim == 1
-        out = self.torch.zeros((self.E, len(kinds), self.mech.V + 1, self.N), dtype=self.torch.float64, device=self.device)
+        if out is None:
+            out = self.torch.zeros((self.E, len(kinds), self.mech.V + 1, self.N), dtype=self.torch.float64,
+                                   device=self.device)
+        assert out.is_cuda and out.dtype == self.torch.float64 and out.is_contiguous() \
+            and out.numel() == self.E*len(kinds)*(self.mech.V + 1)*self.N, "sensitivity buffer must be [E][NP][V+1][N]"
         self._call("rmt_n2_steady_sens", _ptr(y), len(kinds), kinds.ctypes.data_as(C.POINTER(C.c_int)),
                    indices.ctypes.data_as(C.POINTER(C.c_int)), _ptr(out))
         return out
+
+    def fit_step(self, y, sens, loop, k):
+        """Queue pass ``k`` of a fit on the device's stream, behind steady_march and steady_sens on this handle
+        (csrc/fit_kernels.inc): the residuals and their reduction over the members (the experiments) from the state y and
+        the sensitivity buffer ``sens``, then the Levenberg-Marquardt step, which writes slice k of the loop's log and the
+        trial values into the fitted columns of this device's rows.  ``loop``: the run's FitLoop (n2.py).  Nothing is
+        copied or synchronised.  Needs the sensitivity unit (sens_plan) in fp64."""
+        self._chk_state(y)
+        if str(self.defines.get(sensitivity.DEFINE, "0")) != "1" or self.fp32:
+            raise hipbind.RmtN2Error("fit_step needs the sensitivity unit (sens_plan) in fp64")
+        P = len(loop.columns)
+        assert loop.E == self.E and sens.is_cuda and sens.dtype == self.torch.float64 and sens.is_contiguous() \
+            and sens.numel() == self.E*P*(self.mech.V + 1)*self.N, "sensitivity buffer must be [E][NP][V+1][N]"
+        loop.kernel.step(self.h, y.data_ptr(), sens.data_ptr(), self._stats.data_ptr(), self.mech.S, self.mech.V, self.N,
+                         loop.columns, loop.meas.data_ptr(), loop.MQ, loop.contrib.data_ptr(), loop.pred.data_ptr(),
+                         loop.state.data_ptr(), loop.log[k].data_ptr(), loop.tolerance, loop.damping)
 
     def sens_status(self):
         """The status words of the handle steady_sens ran on, read and cleared (synchronises)."""

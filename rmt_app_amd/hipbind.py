@@ -96,6 +96,12 @@ def lib():
     L.rmt_n2_control_destroy.argtypes = [vp]
     L.rmt_n2_control_destroy.restype = None
     L.rmt_n2_control_update.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int]
+    L.rmt_n2_fit_source.restype = cp
+    L.rmt_n2_fit_create.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+    L.rmt_n2_fit_destroy.argtypes = [vp]
+    L.rmt_n2_fit_destroy.restype = None
+    L.rmt_n2_fit_step.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), vp, C.c_int,
+                                  vp, vp, vp, vp, dbl, dbl]
     L.rmt_n2_hiprtc_path.restype = cp
     L.rmt_n2_compile_options.restype = cp
     if L.rmt_n2_abi_version() != ABI_VERSION:
@@ -194,6 +200,36 @@ class Control(_SideModule):
             return C.c_void_p(p) if p else None
         check(lib().rmt_n2_control_update(self.h, handle, ptr(y_ptr), int(V), int(N), ptr(params_ptr), ptr(setpoint_ptr),
                                           ptr(state_ptr), ptr(log_ptr), int(tail_at), int(field), int(bool(hold))))
+
+
+FIT_OPTS = "-ffp-contract=off"           # both fit kernels: one rounded fp64 operation each, reproducible in numpy
+
+
+def fit_source():
+    """The fit's translation unit (csrc/fit_kernels.inc, embedded in the library next to the template)."""
+    return lib().rmt_n2_fit_source().decode()
+
+
+def fit_code(arch="gfx950"):
+    """Code object of the two fit kernels, compiled with floating-point contraction off (_side_code)."""
+    return _side_code("fit", fit_source(), arch, FIT_OPTS)
+
+
+class Fit(_SideModule):
+    """rmt_n2_fit on the current device: the residual reduction and the Levenberg-Marquardt step of solver-config "fit"
+    (include/rmt_n2.h).  Independent of any mechanism; ``step`` enqueues its two kernels on the stream of the N2 handle
+    whose device rows it writes."""
+    kind, code_for = "fit", staticmethod(fit_code)
+
+    def step(self, handle, y_ptr, sens_ptr, stats_ptr, S, V, N, columns, meas_ptr, MQ, contrib_ptr, pred_ptr, state_ptr,
+             log_ptr, tolerance, damping):
+        """Enqueue one pass (residuals, then the update); nothing is synchronised."""
+        def ptr(p):
+            return C.c_void_p(p) if p else None
+        cols = (C.c_int*len(columns))(*[int(c) for c in columns])
+        check(lib().rmt_n2_fit_step(self.h, handle, ptr(y_ptr), ptr(sens_ptr), ptr(stats_ptr), int(S), int(V), int(N),
+                                    len(columns), cols, ptr(meas_ptr), int(MQ), ptr(contrib_ptr), ptr(pred_ptr),
+                                    ptr(state_ptr), ptr(log_ptr), float(tolerance), float(damping)))
 
 
 def compile_source(source, arch="gfx950", extra_opts=""):

@@ -11,7 +11,7 @@ from timeit import default_timer as timer
 
 import numpy as np
 
-from . import campaign, control, hipbind, initial, launches, monitor, plan, profile, schedule, sensitivity
+from . import campaign, control, fit, hipbind, initial, launches, monitor, plan, profile, schedule, sensitivity
 # (the two lists below are also the re-exports: every public name of codeplan and device stays importable from here)
 from .codeplan import (  # noqa: F401
     FEATURE_DEFINES, KC_MAX_AGE, KC_REFRESH, MARCH_BLOCK, MAX_CHUNKS, N_CUS, CodePlan, campaign_plan, campaign_policy_plan,
@@ -656,6 +656,114 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
     return res
 
 
+class FitLoop:
+    """The device side of one fit (fit.Fit): the kernels' module and their buffers - the measurement table [E][MQ][3], the
+    experiments' contributions [E][46] and predictions [E][MQ], the LM state [80] and the log [passes][68], read once per
+    batch of iterations."""
+
+    def __init__(self, ft, dev, columns, passes):
+        torch = dev.torch
+        self.E, self.MQ, self.columns = ft.E, ft.MQ, list(columns)
+        self.tolerance, self.damping = ft.tolerance, ft.damping
+        with torch.cuda.device(dev.device):
+            self.kernel = hipbind.Fit(device_arch(dev.device))
+        self.meas = torch.from_numpy(np.ascontiguousarray(ft.table())).to(dev.device)
+        self.contrib = torch.zeros((ft.E, fit.CONTRIB), dtype=torch.float64, device=dev.device)
+        self.pred = torch.zeros((ft.E, ft.MQ), dtype=torch.float64, device=dev.device)
+        self.state = torch.zeros(fit.STATE, dtype=torch.float64, device=dev.device)
+        self.log = torch.zeros((passes, fit.LOG), dtype=torch.float64, device=dev.device)
+
+    def close(self):
+        self.kernel.close()
+
+
+def run_fit(modelInput, ft, pack_all, result):
+    """solver-config "fit" (fit.py): Levenberg-Marquardt over the steady states of all experiments at once.  Opens the
+    experiments' rows on ONE handle of the sensitivity unit whose per-reactor inputs hold the fitted constants (sens_plan)
+    and queues per iteration rmt_n2_steady_march, rmt_n2_steady_sens and rmt_n2_fit_step back to back; the log comes to the
+    host once per "batch" of iterations, and a finishing pass behind `converged` leaves state, sensitivities, predictions
+    and J^T J of the accepted parameters on the device.  March flags of rejected trials are expected: failures are judged
+    from the log, the sticky flag words are cleared before the finishing pass and checked after it."""
+    start = timer()
+    cfg = modelInput['solver-config']
+    zNo = int(cfg.get('zNo', solverSetting['N2']['zNo']))
+    inputs = ft.members(modelInput)
+    sens = ft.sensitivity()
+    mech = plan.Mechanism(modelInput, params=sens.unit_params(mechanism_for(modelInput, inputs, cfg).params))
+    pairs = [plan.member_constants(mi, mech, zNo) for mi in inputs]
+    named, rows = [nm for nm, _ in pairs], np.array([r for _, r in pairs])
+    columns = ft.columns(mech)
+    initial_values = rows[0, plan.MEMBER_FIXED + mech.S + np.array(columns)].copy()
+    kinds, indices = sens.descriptors(mech)
+    cp = sens_plan(mech, zNo, ft.NP, None, rows)
+    dev = device_cls()(mech, rows, zNo, block=cp.block, npt=cp.npt, defines=cp.defines, specialize=False,
+                       features=cp.features)
+    loop = None
+    try:
+        loop = FitLoop(ft, dev, columns, ft.max_iterations + 1)
+        y = dev.to_device(plan.initial_states(named, mech, zNo, plan.initial_state))
+        raw = dev.torch.zeros((ft.E, ft.NP, mech.V + 1, zNo), dtype=dev.torch.float64, device=dev.device)
+        tol, its = initial.DEFAULTS["tolerance"], initial.DEFAULTS["max-iterations"]
+
+        def queue(k):
+            dev.steady_march(y, tol, its)
+            dev.steady_sens(y, kinds, indices, raw)
+            dev.fit_step(y, raw, loop, k)
+
+        def describe(row):
+            return "cost %.12g at %s" % (row[1], ", ".join("%s = %.12g" % (nm, v) for nm, v in
+                                                           zip(ft.names, row[fit.LOG_PCUR:fit.LOG_PCUR + ft.NP])))
+        logs, n, done = [], 0, False
+        while n < ft.max_iterations and not done:
+            hi = min(ft.max_iterations, n + ft.batch)
+            for k in range(n, hi):
+                queue(k)
+            for row in loop.log[n:hi].cpu().numpy():
+                logs.append(row)
+                status = int(row[7])
+                if status & fit.FIRST_FAILED:
+                    raise RuntimeError("solver-config 'fit': the steady-state march failed (or a prediction is not finite) "
+                                       "for %d of the %d experiments at the starting values" % (int(row[6]), ft.E))
+                if status & fit.NOT_POSITIVE:
+                    raise RuntimeError("solver-config 'fit': J^T J + lambda D is not positive definite after 8 increases of "
+                                       "lambda in iteration %d (%s): the parameters are not identifiable from these data"
+                                       % (len(logs), describe(row)))
+                if row[5] != 0.0:
+                    done = True
+                    break
+            n = hi
+        if not done:
+            raise RuntimeError("solver-config 'fit': no convergence within %d iterations ('max-iterations'): last %s"
+                               % (len(logs), describe(logs[-1])))
+        dev.status()                                    # (read and cleared: what rejected trials flagged)
+        queue(ft.max_iterations)                        # the finishing pass: frozen, everything at the accepted values
+        last = loop.log[ft.max_iterations].cpu().numpy()
+        flags = dev.status()
+        err = flag_error(flags)
+        if err is not None or last[6] != 0.0:
+            st = dev.march_result()[0]
+            e = int(np.nonzero(flags)[0][0]) if err is not None else -1
+            raise RuntimeError("solver-config 'fit': the steady-state march failed at the accepted parameters (%s)%s"
+                               % (describe(last), "" if e < 0 else ": node %d of experiment %d: %s"
+                                  % (int(st["failed-node"][e]), e, err)))
+        Yh, pred = y.cpu().numpy(), loop.pred.cpu().numpy()
+        dstats = {"launches": 4*(n + 1), "iterations": len(logs), "passes": n + 1,
+                  "accepted": int(sum(r[4] for r in logs)), "rejected": int(sum(1 - r[4] for r in logs))}
+    finally:
+        if loop is not None:
+            loop.close()
+        dev.close()
+    packs = pack_all(Yh, named, mech, zNo, 0.0)
+    res = result([packs[0]], modelInput, zNo, None)
+    res["computation-time"] = np.round(timer() - start, ROUND_FUN_ACCURACY)
+    res["device-stats"] = dstats
+    res["ensemble"] = [result([p], mi, zNo, None) for p, mi in zip(packs, inputs)]
+    for e, member in enumerate(res["ensemble"]):
+        member[fit.KEY] = ft.member_entry(e, pred[e])
+    res[fit.KEY] = ft.result_entry(np.array(logs), initial_values, last)
+    return res
+
+
 RunKeys = namedtuple("RunKeys", "sched ctl forced_by mon ini prof sens")
 
 
@@ -826,6 +934,12 @@ def run_n2(modelInput, members_inputs=None):
         if len(named) == 1 and not outlet:
             return [pack_interval(Yg[0], named[0], mech, zNo, t1, modelId)]
         return pack_intervals(Yg, named, mech, zNo, t1, modelId)
+    # "fit": kinetic parameter estimation from steady-state data (fit.py) - no integration in time; absent = None = exactly
+    # the run without it
+    ft = fit.parse(modelInput)
+    if ft is not None:
+        fit.parse(modelInput, multi_rank=active_ranks(ft.E) is not None)
+        return run_fit(modelInput, ft, pack_all, lambda dataPack, mi, zNo, opTSpan: {"dataPack": dataPack})
     sensitivity.parse(modelInput, members_inputs)      # (validation before any device work: not with "deactivation")
     # "deactivation": a time-on-stream run of the quasi-steady bed (campaign.py) - no integration in time; absent = None =
     # exactly the run without it

@@ -42,8 +42,11 @@ def rmtExe(modelInput):
         check_profile(modelInput)             # solver-config 'axial-profile': model N2 only
         from .campaign import check_model as check_campaign
         check_campaign(modelInput)            # solver-config 'deactivation': model N2 only
+        from .fit import check_model as check_fit, parse as parse_fit
+        check_fit(modelInput)                 # solver-config 'fit': model N2 only
         if modelType == "N2":
             from .n2 import run_n2
+            parse_fit(modelInput)             # (a "fit" beside "ensemble" raises before the members are expanded)
             ensemble = modelInput['solver-config'].get('ensemble')
             if ensemble is not None:
                 from .ensemble import expand_members

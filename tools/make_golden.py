@@ -5,13 +5,14 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign policy sensitivity  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign policy sensitivity fit  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
 coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
 closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|syn12]: discrete steady states of model N2,
 G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18; campaign[=DA|DB|DC|DI]:
 time-on-stream runs with catalyst deactivation, G19; policy[=PA|PS|PB]: the coolant policy of such a run, G20;
-sensitivity[=SA|SB|SK|SW]: parametric sensitivities of the steady state, G21 - like G13..G15 these
+sensitivity[=SA|SB|SK|SW]: parametric sensitivities of the steady state, G21; fit[=FA|FB|FN]: kinetic parameter
+estimation from steady-state data, G22 - like G13..G15 these
 run SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
@@ -1553,6 +1554,49 @@ def g_sensitivity(which=None):
               % (name, time.time() - t0, out["delta"], rel.max(), out["residual"]), flush=True)
 
 
+# ------------------------------------------------------------------ G22: kinetic parameter estimation from steady-state data
+# (solver-config "fit", rmt_app_amd/fit.py).  tests/fit_ref.py: data from steady states of the oracle at p_true (the recipe
+# and the gate of G17), the fit by scipy.optimize.least_squares with central differences of those steady states as the
+# Jacobian; nothing of the product is imported.  A case is refused (SystemExit) when a steady state at the start or at
+# p_true ends above the gate, when the noise-free fit misses p_true by more than 1e-7 relative, or when the
+# Marquardt-scaled cond(H) at the optimum exceeds 1e8 - then widen the spread of the conditions, not the cap.
+def g_fit(which=None):
+    import fit_ref as FR
+    from oracle import n2_oracle as O
+    path = os.path.join(GOLD, "g22_fit.json")
+    meta = {"cases": {}, "gate": FR.CR.GATE, "cond_cap": FR.COND_CAP, "true_cap": FR.TRUE_CAP, "zNo": FR.ZNO,
+            "sigma": FR.SIGMA, "noise_seed": FR.NOISE_SEED, "p_true": FR.P_TRUE, "conditions": FR.conditions(),
+            "labels": [FR.labels(e) for e in range(len(FR.conditions()))],
+            "reference": "steady states of oracle.n2_oracle.make_rhs_vec from campaign_ref.steady_state (cold start) and "
+                         "sens_ref.polish; scipy.optimize.least_squares (trf, x_scale 'jac', tolerances 1e-14) with "
+                         "central differences (1e-4 |p|) of those steady states as the Jacobian (tests/fit_ref.py)"}
+    if which in (None, "states"):
+        # the experiments' steady states at p_true (the same for every case): where the CPU test of the reference starts
+        ref = FR.Reference(O, FR.NAMES, log=lambda msg: print("G22 %s" % msg, flush=True))
+        ref.predict(np.array([FR.P_TRUE[nm] for nm in FR.NAMES]), keep=True, gate=True)
+        np.savez_compressed(os.path.join(GOLD, "g22_fit_states.npz"), states=np.array(ref.last))
+        print("G22 states written: worst max|f| %.2e" % ref.worst, flush=True)
+        if which == "states":
+            return
+    for name in ([which] if which else list(FR.CASES)):
+        t0 = time.time()
+        out = FR.run_case(O, name, log=lambda msg: print("G22 %s" % msg, flush=True))
+        cov = out["covariance"]
+        np.savez_compressed(os.path.join(GOLD, "g22_fit_%s.npz" % name), measured=out["measured"],
+                            predicted_true=out["predicted_true"], p_ref=out["p_ref"],
+                            p_ref_noise_free=out["p_ref_noise_free"], cost=out["cost"], hessian=out["hessian"],
+                            covariance=cov if cov is not None else np.zeros((0, 0)))
+        if os.path.exists(path):
+            with open(path) as fh:
+                meta["cases"] = json.load(fh)["cases"]
+        meta["cases"][name] = dict(FR.CASES[name], p_ref=[float(v) for v in out["p_ref"]], cost=float(out["cost"]),
+                                   cond=float(out["cond"]), residual=float(out["residual_gate"]))
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+        print("G22 %s written (%.0f s): p_ref %s, cost %.6e, scaled cond(H) %.3e, worst max|f| %.2e"
+              % (name, time.time() - t0, out["p_ref"], out["cost"], out["cond"], out["residual_gate"]), flush=True)
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1596,6 +1640,8 @@ def main(argv):
             g_policy(what.split("=", 1)[1] if "=" in what else None)
         elif what == "sensitivity" or what.startswith("sensitivity="):
             g_sensitivity(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "fit" or what.startswith("fit="):
+            g_fit(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

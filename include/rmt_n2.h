@@ -218,6 +218,24 @@ int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, int64_t max_i
  * can see flags every member).  Enqueues ONE kernel on the handle's stream and does not synchronise.  A member with a
  * singular node gets RMT_N2_FLAG_NONFINITE and NaN in its rows at that node; the nodes behind it are not written. */
 int rmt_n2_steady_sens(rmt_n2_handle* h, const void* y, int n_params, const int* kinds, const int* indices, double* out);
+/* Frequency response of that steady state (solver-config "frequency-response", csrc/kernels/74_frequency.inc): for a
+ * harmonic disturbance exp(i w t) of a value of the member's device row the linearised dynamic model answers with
+ * s exp(i w t), (a_z + i w I) s_z = U D s_(z-1) + (df/dP) pi_z + df/dp - the tangent march of rmt_n2_steady_sens with a
+ * complex shift, one (member, frequency) pair per lane; w = 0 gives the sensitivities.  y DEVICE double [E][V][N] (the
+ * converged state); kinds / indices HOST arrays of n_inputs ints as for rmt_n2_steady_sens, kinds 0..3 only,
+ * 1 <= n_inputs <= 4; omegas_host HOST [n_freq] doubles >= 0 in radians per unit of the right-hand side's time,
+ * 1 <= n_freq <= 4096; peak_nodes_host HOST [E] ints: the node whose rows are returned beside the outlet's (a node outside
+ * 0..N-1: none).  out_host HOST doubles, complex numbers as (re, im) pairs, in the scaled units of the state per unit of
+ * the row value, row V = d P_z:
+ *   [E][n_freq][n_inputs][2][V+1][2]      the rows of the outlet node (slot 0) and of the member's peak node (slot 1)
+ *   [E][n_freq][n_inputs][V+1][N][2]      every node - only with profile != 0, else this part is absent
+ *   [E][n_freq]                           the node at which the lane stopped (-1: none), as a double
+ * Needs a code object generated with RMT_FREQ 1 and RMT_FREQ_NP == n_inputs beside RMT_SENS and RMT_WITH_MARCH, else it
+ * returns an error.  Uploads, enqueues ONE kernel on the handle's stream, copies back and synchronises.  A lane with a
+ * singular or non-finite node sets RMT_N2_FLAG_NONFINITE on its member, writes NaN at that node (and into both slots) and
+ * stops there. */
+int rmt_n2_steady_freq(rmt_n2_handle* h, const void* y, int n_inputs, const int* kinds, const int* indices, int n_freq,
+                       const double* omegas_host, const int* peak_nodes_host, int profile, double* out_host);
 /* Time-on-stream campaigns (solver-config "deactivation", csrc/kernels/72_campaign.inc): the bed is quasi-steady, its
  * catalyst activity a_n follows da_n/dt = -k_d(T_n) (a_n - a_inf)^m, k_d(T) = k_ref exp(-(Ed/R)(1/T - 1/Tref)), T_n the
  * node's temperature in kelvin (the member's inlet temperature in an iso-thermal run).  The three calls need a handle whose

@@ -5,7 +5,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import campaign, hipbind, plan, profile, schedule, sensitivity
+from . import campaign, frequency, hipbind, plan, profile, schedule, sensitivity
 
 FEATURE_DEFINES = {"ros4": "RMT_WITH_ROS4", "n1": "RMT_WITH_N1", "march": "RMT_WITH_MARCH"}
 MARCH_BLOCK = 64         # csrc/kernels/71_steady_march.inc: one reactor per lane, one wave per workgroup
@@ -340,6 +340,16 @@ def sens_plan(mech, N, n_params, defines=None, rows=None):
     cp = march_plan(mech, N, defines, rows)
     return CodePlan(cp.block, cp.npt, cp.lds_state,
                     {**cp.defines, sensitivity.DEFINE: "1", sensitivity.DEFINE_NP: str(int(n_params))}, cp.features)
+
+
+def freq_plan(mech, N, n_inputs, defines=None, rows=None):
+    """The code object of solver-config "frequency-response" (csrc/kernels/74_frequency.inc): the sensitivity unit of the
+    run's own mechanism (sens_plan with RMT_SENS_NP = n_inputs) plus RMT_FREQ and RMT_FREQ_NP - rmt_n2_steady_freq beside
+    rmt_n2_steady_sens and rmt_n2_steady_march.  It always lives on a handle of its own (N2Device.attach_frequency): every
+    other unit of the run, the march and the sensitivity unit included, is what it is without the key."""
+    cp = sens_plan(mech, N, n_inputs, defines, rows)
+    return CodePlan(cp.block, cp.npt, cp.lds_state,
+                    {**cp.defines, frequency.DEFINE: "1", frequency.DEFINE_NP: str(int(n_inputs))}, cp.features)
 
 
 def code_plans(mech, N, fp32=False, E=None, block=None, npt=None, lds_state=None, defines=None, features=(),

@@ -315,4 +315,3 @@ extern "C" __global__ __launch_bounds__(64) void rmt_n2_steady_sens(
 }
 #endif  // RMT_HOST_EMULATION
 #endif  // RMT_SENS
-//<<< RMT_SENS

@@ -65,7 +65,7 @@ struct rmt_n2_handle {
     hipFunction_t f_rhs = nullptr, f_rk4_reg = nullptr, f_rk4_mem = nullptr, f_rk45_reg = nullptr,
                   f_rk45_mem = nullptr, f_multistep = nullptr, f_rk4_chain = nullptr, f_ros4 = nullptr, f_n1 = nullptr,
                   f_ros4_chain = nullptr, f_rk45_chain = nullptr, f_rk4_redo = nullptr, f_rk4_chain_redo = nullptr,
-                  f_march = nullptr, f_campaign = nullptr, f_policy = nullptr, f_sens = nullptr;
+                  f_march = nullptr, f_campaign = nullptr, f_policy = nullptr, f_sens = nullptr, f_freq = nullptr;
     unsigned long long* d_rings = nullptr;   // tagged-word links of the chained stiff stepper: rings, decision slots, abort words
     size_t ring_bytes = 0;
     double* d_members1 = nullptr;
@@ -276,6 +276,7 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
         {"rmt_n2_campaign_step", &rmt_n2_handle::f_campaign, false},
         {"rmt_n2_campaign_policy_step", &rmt_n2_handle::f_policy, false},
         {"rmt_n2_steady_sens", &rmt_n2_handle::f_sens, false},
+        {"rmt_n2_steady_freq", &rmt_n2_handle::f_freq, false},
     };
     for (const auto& k : kernels) {
         const hipError_t e = hipModuleGetFunction(&(h->*k.f), h->module, k.name);
@@ -818,6 +819,78 @@ extern "C" int rmt_n2_steady_sens(rmt_n2_handle* h, const void* y, int n_params,
     void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&n_params, (void*)&desc, (void*)&out,
                     (void*)&h->d_flags};
     return launch_lanes(h, h->f_sens, args);
+}
+
+// solver-config "frequency-response" (kernels/74_frequency.inc): the shifted tangent march over the converged state, one
+// (member, frequency) pair per lane.  Frequencies and peak nodes are HOST arrays, the result comes back to the HOST: the
+// call uploads, launches once, copies back and synchronises; its device buffers live for the call.
+#define RMT_N2_FREQ_MAX_INPUTS 4
+#define RMT_N2_FREQ_MAX_FREQUENCIES 4096
+extern "C" int rmt_n2_steady_freq(rmt_n2_handle* h, const void* y, int n_inputs, const int* kinds, const int* indices,
+                                  int n_freq, const double* omegas_host, const int* peak_nodes_host, int profile,
+                                  double* out_host) {
+    if (!h || !y || !kinds || !indices || !omegas_host || !peak_nodes_host || !out_host)
+        return fail("rmt_n2_steady_freq: null argument");
+    if (!h->f_freq || !h->f_march)
+        return fail("rmt_n2_steady_freq: this handle's code object has no rmt_n2_steady_freq (generate it with RMT_FREQ and "
+                    "RMT_FREQ_NP beside RMT_SENS and RMT_WITH_MARCH)");
+    if (h->fp32) return fail("rmt_n2_steady_freq: fp64 only");
+    if (n_inputs < 1 || n_inputs > RMT_N2_FREQ_MAX_INPUTS)
+        return fail("rmt_n2_steady_freq: 1..%d inputs (got %d)", RMT_N2_FREQ_MAX_INPUTS, n_inputs);
+    if (n_freq < 1 || n_freq > RMT_N2_FREQ_MAX_FREQUENCIES)
+        return fail("rmt_n2_steady_freq: 1..%d frequencies (got %d)", RMT_N2_FREQ_MAX_FREQUENCIES, n_freq);
+    struct { int kind[RMT_N2_SENS_MAX], index[RMT_N2_SENS_MAX]; } desc;
+    std::memset(&desc, 0, sizeof(desc));
+    for (int p = 0; p < n_inputs; ++p) {
+        const int k = kinds[p], i = indices[p];
+        if (k < 0 || k > 3 || i < 0 || (k == 3 && i >= h->S) || (k < 3 && i != 0))
+            return fail("rmt_n2_steady_freq: input %d: kind %d (0 TM, 1 THETA_IN, 2 P0, 3 CIN[index]) with index %d is out of "
+                        "range (S = %d)", p, k, i, h->S);
+        desc.kind[p] = k;
+        desc.index[p] = i;
+    }
+    for (int f = 0; f < n_freq; ++f)
+        if (!(omegas_host[f] >= 0.0) || !std::isfinite(omegas_host[f]))
+            return fail("rmt_n2_steady_freq: frequency %d is %g (finite and >= 0)", f, omegas_host[f]);
+    PROFILE_READY(h);
+    ON_DEVICE(h);
+    const size_t lanes = (size_t)h->E * (size_t)n_freq, rows = (size_t)n_inputs * (size_t)(h->V + 1) * 2;
+    const size_t n_out = lanes * rows * 2, n_tab = profile ? lanes * rows * (size_t)h->N : 0, n_all = n_out + n_tab + lanes;
+    const size_t bytes = n_all * sizeof(double) + (size_t)n_freq * sizeof(double) + (size_t)h->E * sizeof(int);
+    if ((lanes + 63) / 64 > 0x7fffffffULL) return fail("rmt_n2_steady_freq: %zu lanes are more than one grid holds", lanes);
+    char* buf = nullptr;
+    HIP_OK(hipMalloc((void**)&buf, bytes));
+    double* d_out = (double*)buf;
+    double* d_tab = profile ? d_out + n_out : nullptr;
+    double* d_failed = d_out + n_out + n_tab;
+    double* d_omegas = d_out + n_all;
+    int* d_peak = (int*)(d_omegas + n_freq);
+    int rc = 0;
+#define FREQ_OK(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess && !rc) rc = fail("%s failed: %s", #call, hipGetErrorString(e_));     \
+    } while (0)
+    FREQ_OK(hipMemsetAsync(d_out, 0, n_all * sizeof(double), h->stream));
+    if (!rc) FREQ_OK(hipMemcpyAsync(d_omegas, omegas_host, (size_t)n_freq * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!rc) FREQ_OK(hipMemcpyAsync(d_peak, peak_nodes_host, (size_t)h->E * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (!rc) FREQ_OK(hipStreamSynchronize(h->stream));            // (the host arrays are pageable: the copies have left them)
+    if (!rc) {
+        int N = h->N, E = h->E;
+        void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&n_freq, (void*)&n_inputs, (void*)&desc,
+                        (void*)&d_omegas, (void*)&d_peak, (void*)&profile, (void*)&d_out, (void*)&d_tab, (void*)&d_failed,
+                        (void*)&h->d_flags};
+        FREQ_OK(hipEventRecord(h->ev0, h->stream));
+        if (!rc) FREQ_OK(hipModuleLaunchKernel(h->f_freq, (unsigned)((lanes + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args,
+                                               nullptr));
+        if (!rc) FREQ_OK(hipEventRecord(h->ev1, h->stream));
+        if (!rc) h->timed = true;
+    }
+    if (!rc) FREQ_OK(hipMemcpyAsync(out_host, d_out, n_all * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    FREQ_OK(hipStreamSynchronize(h->stream));
+    FREQ_OK(hipFree(buf));
+#undef FREQ_OK
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------- campaign

@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import campaign, hipbind, initial, monitor, plan, sensitivity
-from .codeplan import code_plan, compile_plan, device_arch, forced_tail, is_forced, is_profiled, march_plan, sens_plan
+from . import campaign, frequency, hipbind, initial, monitor, plan, sensitivity
+from .codeplan import code_plan, compile_plan, device_arch, forced_tail, freq_plan, is_forced, is_profiled, march_plan, sens_plan
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS
 
@@ -132,6 +132,7 @@ class N2Device:
         self._stats = torch.zeros((self.E, 4), dtype=torch.float64, device=self.device)
         self.march = None       # a second device of the same rows with the steady-state march (attach_march)
         self.sens = None        # ... and a third with the sensitivity unit, where that needs a mechanism of its own
+        self.freq = None        # ... and one with the frequency unit (attach_frequency)
         self.use_current_stream()
         self.profile = None
         if profile is not None:
@@ -192,7 +193,7 @@ class N2Device:
                                      % ((self.E, 2, self.N), table.shape))
         self._call("rmt_n2_set_profile", _doubles(table))
         self.profile = table
-        for dev in (self.march, self.sens):
+        for dev in (self.march, self.sens, self.freq):
             if dev is not None:
                 dev.set_profile(table)
 
@@ -210,10 +211,10 @@ class N2Device:
         if getattr(self, "_mon", None) is not None:
             self._mon.close()
             self._mon = None
-        for dev in (getattr(self, "march", None), getattr(self, "sens", None)):
+        for dev in (getattr(self, "march", None), getattr(self, "sens", None), getattr(self, "freq", None)):
             if dev is not None:
                 dev.close()
-        self.march = self.sens = None
+        self.march = self.sens = self.freq = None
         if getattr(self, "h", None):
             hipbind.lib().rmt_n2_destroy(self.h)
             self.h = None
@@ -340,6 +341,49 @@ class N2Device:
         self._call("rmt_n2_steady_sens", _ptr(y), len(kinds), kinds.ctypes.data_as(C.POINTER(C.c_int)),
                    indices.ctypes.data_as(C.POINTER(C.c_int)), _ptr(out))
         return out
+
+    def attach_frequency(self, n_inputs):
+        """A handle of its own on the same member rows whose code object is the frequency unit (freq_plan, solver-config
+        "frequency-response"): the stepper's, the march's and the sensitivity unit's code objects stay what they are without
+        the key.  steady_freq then goes through it."""
+        if self.freq is None:
+            if self.fp32 or getattr(self.mech, "model", "N2") != "N2":
+                raise hipbind.RmtN2Error("the frequency sweep is for model N2 in fp64")
+            cp = freq_plan(self.mech, self.N, n_inputs, self.defines, self.members)
+            self.freq = N2Device(self.mech, self.members, self.N, block=cp.block, npt=cp.npt, device=self.device.index,
+                                 defines=cp.defines, specialize=False, features=cp.features, profile=self.profile)
+        return self
+
+    def steady_freq(self, y, kinds, indices, omegas, peak_nodes, profile=False):
+        """Frequency response of the steady state y (rmt_n2_steady_freq): (rows [E][F][NP][2][V+1] complex - slot 0 the
+        outlet node, slot 1 node peak_nodes[e] -, table [E][F][NP][V+1][N] complex or None without ``profile``, failed
+        [E][F] ints: the node a lane stopped at, -1 none) as numpy arrays, in the scaled units of the state per unit of the
+        row value (row V: the pressure).  ``omegas`` [F] in radians per unit of model time.  Blocking: one upload, ONE launch,
+        one copy back; status() reads the flags.  Needs the frequency unit (freq_plan) with RMT_FREQ_NP = len(kinds) -
+        this handle's own, or the one attach_frequency made."""
+        if self.freq is not None:
+            return self.freq.steady_freq(y, kinds, indices, omegas, peak_nodes, profile)
+        self._chk_state(y)
+        if str(self.defines.get(frequency.DEFINE, "0")) != "1" or int(self.defines[frequency.DEFINE_NP]) != len(kinds):
+            raise hipbind.RmtN2Error("steady_freq needs the frequency unit (freq_plan) with RMT_FREQ_NP = %d" % len(kinds))
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        omegas = np.ascontiguousarray(omegas, dtype=np.float64)
+        peak_nodes = np.ascontiguousarray(peak_nodes, dtype=np.int32)
+        assert kinds.shape == indices.shape and kinds.ndim == 1 and omegas.ndim == 1 and peak_nodes.shape == (self.E,)
+        E, F, NP, V1, N = self.E, len(omegas), len(kinds), self.mech.V + 1, self.N
+        n_out, n_tab = E*F*NP*2*V1*2, E*F*NP*V1*N*2 if profile else 0
+        buf = np.zeros(n_out + n_tab + E*F)
+        ints = C.POINTER(C.c_int)
+        self._call("rmt_n2_steady_freq", _ptr(y), NP, kinds.ctypes.data_as(ints), indices.ctypes.data_as(ints), F,
+                   _doubles(omegas), peak_nodes.ctypes.data_as(ints), int(bool(profile)), _doubles(buf))
+        rows = buf[:n_out].view(np.complex128).reshape(E, F, NP, 2, V1)
+        table = buf[n_out:n_out + n_tab].view(np.complex128).reshape(E, F, NP, V1, N) if profile else None
+        return rows, table, buf[n_out + n_tab:].astype(np.int64).reshape(E, F)
+
+    def freq_status(self):
+        """The status words of the handle steady_freq ran on, read and cleared (synchronises)."""
+        return (self.freq if self.freq is not None else self).status()
 
     def fit_step(self, y, sens, loop, k):
         """Queue pass ``k`` of a fit on the device's stream, behind steady_march and steady_sens on this handle
@@ -562,6 +606,16 @@ class AutoStepper:
 
     def sens_status(self):
         return self.d45.sens_status()
+
+    def attach_frequency(self, n_inputs):
+        self.d45.attach_frequency(n_inputs)
+        return self
+
+    def steady_freq(self, y, kinds, indices, omegas, peak_nodes, profile=False):
+        return self.d45.steady_freq(y, kinds, indices, omegas, peak_nodes, profile)
+
+    def freq_status(self):
+        return self.d45.freq_status()
 
     def steady_march(self, y, tol=initial.DEFAULTS["tolerance"], max_iter=initial.DEFAULTS["max-iterations"]):
         """the steady-state march on the rows of the explicit device (both devices hold the same rows)"""

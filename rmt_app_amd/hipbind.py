@@ -75,6 +75,8 @@ def lib():
     L.rmt_n1_profile.argtypes = [vp, C.POINTER(dbl), vp, C.c_int, dbl, dbl, dbl, i64, vp]
     L.rmt_n2_steady_march.argtypes = [vp, vp, dbl, i64, vp]
     L.rmt_n2_steady_sens.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+    L.rmt_n2_steady_freq.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(dbl),
+                                     C.POINTER(C.c_int), C.c_int, C.POINTER(dbl)]
     L.rmt_n2_set_campaign_law.argtypes = [vp, C.POINTER(dbl)]
     L.rmt_n2_campaign_step.argtypes = [vp, vp, dbl, dbl, i64, vp, vp]
     L.rmt_n2_get_profile.argtypes = [vp, C.POINTER(dbl)]

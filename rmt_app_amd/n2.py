@@ -11,13 +11,13 @@ from timeit import default_timer as timer
 
 import numpy as np
 
-from . import campaign, control, fit, hipbind, initial, launches, monitor, plan, profile, schedule, sensitivity
+from . import campaign, control, fit, frequency, hipbind, initial, launches, monitor, plan, profile, schedule, sensitivity
 # (the two lists below are also the re-exports: every public name of codeplan and device stays importable from here)
 from .codeplan import (  # noqa: F401
     FEATURE_DEFINES, KC_MAX_AGE, KC_REFRESH, MARCH_BLOCK, MAX_CHUNKS, N_CUS, CodePlan, campaign_plan, campaign_policy_plan,
     choose_geometry, code_plan, code_plans, compile_mechanism, compile_options, compile_plan, device_arch, device_source,
     forced_literals, forced_mode, forced_tail, forcing_level, is_campaign, is_forced, is_profiled, kc_period, kcache_choice,
-    march_plan, plan_unit, precompile, rk45_block, rk45_geometry, ros4_block, ros4_quad, sens_plan)
+    freq_plan, march_plan, plan_unit, precompile, rk45_block, rk45_geometry, ros4_block, ros4_quad, sens_plan)
 from .device import FLAG_PRESSURE, AutoStepper, N2Device, flag_error, step_counts, stepper_args  # noqa: F401
 from .ensemble import DistributedEnsemble, active_ranks, guarded
 from .settings import DEVICE_DEFAULTS, ROUND_FUN_ACCURACY, solverSetting
@@ -121,7 +121,7 @@ def mechanism_for(modelInput, inputs, cfg):
 
 
 def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=None, npt=None, defines=None,
-                 features=(), forcing=None, march=False, prof=None, sens=None):
+                 features=(), forcing=None, march=False, prof=None, sens=None, freq=None):
     """Device + initial state for the members THIS process integrates.
 
     Single process: all of ``inputs``.  As one rank of a torch.distributed job (``sync``, see
@@ -132,7 +132,9 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
     moves the feed composition, else 1), the rows get their tail, and the host fixes the kernel form (forced_mode).
     ``march`` (solver-config "initial", single process): a second handle on the same rows holds the steady-state march
     (N2Device.attach_march); with ``sens`` (a sensitivity.Sensitivity, solver-config "sensitivity") that handle's code
-    object is the sensitivity unit (sens_plan) and ``sens.mech`` / ``sens.rows`` receive its mechanism and rows.
+    object is the sensitivity unit (sens_plan) and ``sens.mech`` / ``sens.rows`` receive its mechanism and rows; with
+    ``freq`` (a frequency.FrequencyResponse, solver-config "frequency-response") one more handle holds the frequency unit
+    (N2Device.attach_frequency) and ``freq.rows`` receives the rows.
     ``prof`` (a profile.Profile, solver-config "axial-profile", single process): the code object is generated with
     RMT_PROFILE, the table is uploaded before anything is launched, and the host fixes the kernel form by the rule of the
     forced runs (no chained form carries the profile)."""
@@ -161,6 +163,9 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
                         else plan.Mechanism(inputs[0], params=sens.unit_params(mech.params))
                     sens.rows = sens.widen(rows, mech, sens.mech, inputs)
                 dev.attach_march(None if sens is None else (sens.NP, sens.mech, sens.rows))
+                if freq is not None:
+                    freq.rows = rows
+                    dev.attach_frequency(freq.NP)
             except Exception:
                 dev.close()
                 raise
@@ -190,7 +195,7 @@ def open_members(mech, inputs, zNo, pack, init, sync=None, fp32=False, block=Non
 
 
 def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, npt=None, forcing=None, march=False,
-              prof=None, sens=None):
+              prof=None, sens=None, freq=None):
     """The two devices of ivp "hip-auto" (explicit pair in its on-chip geometry, Rosenbrock family) behind one
     AutoStepper; an explicit `block` / `nodes-per-thread` of the solver-config applies to the explicit device."""
     if block is None and (forcing is not None or prof is not None):       # (no chained chunks: they carry neither)
@@ -201,7 +206,7 @@ def open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block=None, np
         b45, n45, d45 = block, npt, {}
     dev45, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=b45, npt=n45,
                                           defines={**(defines or {}), **d45}, forcing=forcing, march=march, prof=prof,
-                                          sens=sens)
+                                          sens=sens, freq=freq)
     def make_ros4():
         return open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=ros4_block(mech.V, zNo, fp32),
                             npt=1, defines=defines, features=("ros4",), forcing=forcing, prof=prof)[0]
@@ -554,6 +559,26 @@ def start_sensitivity(dev, y, sens, named):
     return [sensitivity.result_entry(sens, raw[e], Yh[e], sens.rows[e], named[e], sens.mech) for e in range(raw.shape[0])]
 
 
+def start_frequency(dev, y, fr, named, mech):
+    """solver-config "frequency-response": ONE launch of rmt_n2_steady_freq on the frequency handle over the marched state y,
+    the rows come back once.  Raises FloatingPointError naming member, frequency and node when a node of the shifted
+    tangent march is singular or not finite.  Returns the members' result entries."""
+    kinds, indices = fr.descriptors(mech)
+    Yh = y.cpu().numpy()
+    peaks = [frequency.peak_node(Yh[e], mech, named[e]) for e in range(Yh.shape[0])]
+    rows, table, failed = dev.steady_freq(y, kinds, indices, fr.omegas, peaks, fr.profile)
+    flags = dev.freq_status()
+    if np.any(flags) or np.any(failed >= 0):
+        e = int(np.nonzero(flags)[0][0]) if np.any(flags) else int(np.argwhere(failed >= 0)[0][0])
+        bad = np.nonzero(failed[e] >= 0)[0]
+        f = int(bad[0]) if len(bad) else 0
+        raise FloatingPointError("solver-config 'frequency-response': the shifted node Jacobian is singular (or a response "
+                                 "is not finite) at node %d of member %d at frequency %d (w = %g, flags=0x%x)"
+                                 % (int(failed[e, f]), e, f, fr.omegas[f], int(flags[e])))
+    return [frequency.result_entry(fr, rows[e], None if table is None else table[e], Yh[e], fr.rows[e], named[e], mech)
+            for e in range(Yh.shape[0])]
+
+
 def policy_error(cam, e, first, plog):
     """The exception for member ``e`` whose policy step gave up: ``plog`` [n][4] are its policy log rows from step ``first``
     on; the first row with `saturated` 2 (bracket collapsed) or 3 (evaluation limit) is the step that failed."""
@@ -764,7 +789,7 @@ def run_fit(modelInput, ft, pack_all, result):
     return res
 
 
-RunKeys = namedtuple("RunKeys", "sched ctl forced_by mon ini prof sens")
+RunKeys = namedtuple("RunKeys", "sched ctl forced_by mon ini prof sens freq")
 
 
 def parse_keys(modelInput, members_inputs, ivp, tNo, E, V, ranked, with_schedule):
@@ -776,7 +801,8 @@ def parse_keys(modelInput, members_inputs, ivp, tNo, E, V, ranked, with_schedule
       mon    "monitor": time series between the output times (monitor.py)
       ini    "initial": where the run starts (initial.py); None = the reference's cold start
       prof   "axial-profile": catalyst activity and coolant zones along the bed (profile.py); knows the "device-mode"
-      sens   "sensitivity": parametric sensitivities of the steady state the run starts from (sensitivity.py)"""
+      sens   "sensitivity": parametric sensitivities of the steady state the run starts from (sensitivity.py)
+      freq   "frequency-response": the harmonic response of that steady state (frequency.py)"""
     sched = schedule.parse(modelInput, members_inputs, ivp) if with_schedule else None
     control.check_model(modelInput)
     ctl, forced_by = control.parse(modelInput, members_inputs, ivp, sched, ranked) if with_schedule else (None, sched)
@@ -791,7 +817,8 @@ def parse_keys(modelInput, members_inputs, ivp, tNo, E, V, ranked, with_schedule
     if prof is not None:
         prof.want_mode = modelInput['solver-config'].get('device-mode')
     sens = sensitivity.parse(modelInput, members_inputs, ranked) if with_schedule else None
-    return RunKeys(sched, ctl, forced_by, mon, ini, prof, sens)
+    freq = frequency.parse(modelInput, members_inputs, ranked, V) if with_schedule else None
+    return RunKeys(sched, ctl, forced_by, mon, ini, prof, sens, freq)
 
 
 def run_geometry(ivp, mech, zNo, fp32, block, npt, defines, E_gpu, carried=()):
@@ -836,8 +863,8 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
     mech = mechanism_for(modelInput, inputs, cfg)
     sync = active_ranks(len(inputs)) if members_inputs else None       # one rank of a torchrun job?
     E_gpu = len(inputs) if sync is None else max(sync.counts)
-    sched, ctl, forced_by, mon, ini, prof, sens = parse_keys(modelInput, members_inputs, ivp, tNo, len(inputs), mech.V,
-                                                             sync is not None, with_schedule)
+    sched, ctl, forced_by, mon, ini, prof, sens, freq = parse_keys(modelInput, members_inputs, ivp, tNo, len(inputs),
+                                                                   mech.V, sync is not None, with_schedule)
     # the ONE launch list of the run; a sample that fell on a mark carries that mark's time from here on (result entries)
     walk, sample_times, control_times = launches.merge(
         opT, tNo, forced_by.times if forced_by is not None else (), mon.times if mon is not None else None,
@@ -856,11 +883,11 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
                           cfg.get('device-mode'))
     if ivp == "hip-auto":
         dev, named_local, IV = open_auto(mech, inputs, zNo, pack, init, sync, fp32, defines, block, npt, forcing=forcing,
-                                         march=ini is not None, prof=prof, sens=sens)
+                                         march=ini is not None, prof=prof, sens=sens, freq=freq)
     else:
         dev, named_local, IV = open_members(mech, inputs, zNo, pack, init, sync, fp32=fp32, block=block, npt=npt,
                                             defines=defines, features=("ros4",) if ivp == "hip-ros4" else (),
-                                            forcing=forcing, march=ini is not None, prof=prof, sens=sens)
+                                            forcing=forcing, march=ini is not None, prof=prof, sens=sens, freq=freq)
     # the process that returns the results (rank 0, or the only one) packs EVERY member
     packer = sync is None or sync.rank == 0
     try:
@@ -872,6 +899,7 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         # (the device rows are those of t = 0: a forced run's were attached for its first launch, which starts there)
         started = start_steady(dev, y, ini, mech) if ini is not None else None
         sensed = start_sensitivity(dev, y, sens, named) if sens is not None else None
+        swept = start_frequency(dev, y, freq, named, mech) if freq is not None else None
         packs = [[] for _ in named]
 
         def on_interval(i, t1, Yh):
@@ -911,6 +939,8 @@ def run_dynamic(modelInput, members_inputs, model, pack, init, pack_all, result,
         attach_entries(res, "initial", started)
     if sensed is not None:
         attach_entries(res, sensitivity.KEY, sensed)
+    if swept is not None:
+        attach_entries(res, frequency.KEY, swept)
     if monitors:
         attach_entries(res, "monitor", monitors)
     if sync is not None:
@@ -936,6 +966,7 @@ def run_n2(modelInput, members_inputs=None):
         return pack_intervals(Yg, named, mech, zNo, t1, modelId)
     # "fit": kinetic parameter estimation from steady-state data (fit.py) - no integration in time; absent = None = exactly
     # the run without it
+    frequency.parse(modelInput, members_inputs)        # (validation before any device work: not with "fit", "deactivation")
     ft = fit.parse(modelInput)
     if ft is not None:
         fit.parse(modelInput, multi_rank=active_ranks(ft.E) is not None)

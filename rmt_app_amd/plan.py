@@ -313,7 +313,9 @@ class Mechanism:
         """Complete translation unit: prelude + template with the lowered kinetics spliced in.  The text of the campaign
         step (csrc/kernels/72_campaign.inc, between its two marks) goes into the campaign unit only (RMT_CAMPAIGN): every
         other unit's source, and with it its cache key, is what it is without that file.  The same holds for the text of
-        the sensitivity sweep (csrc/kernels/73_sensitivity.inc) and the sensitivity unit (RMT_SENS)."""
+        the sensitivity sweep (csrc/kernels/73_sensitivity.inc) and the sensitivity unit (RMT_SENS), and for the text of the
+        frequency sweep (csrc/kernels/74_frequency.inc, inside the sensitivity sweep's marks) and the frequency unit
+        (RMT_FREQ beside RMT_SENS)."""
         if "RMT_KINETICS_SOURCE" not in template:
             raise ValueError("kernel template lacks the RMT_KINETICS_SOURCE marker")
         # ... and the text of the sensitivity sweep (csrc/kernels/73_sensitivity.inc, between its two marks) into the
@@ -324,6 +326,12 @@ class Mechanism:
             if _not0(d, "RMT_SENS_NP", "0"):
                 raise ValueError("RMT_SENS_NP: only together with RMT_SENS=1 (n2.sens_plan)")
             template = _cut(template, SENS_MARKS)
+        # ... and the text of the frequency sweep (csrc/kernels/74_frequency.inc, which lies inside the sensitivity sweep's
+        # marks) into the frequency unit only (RMT_FREQ beside RMT_SENS, codeplan.freq_plan)
+        if not (sens and _is1(d, "RMT_FREQ")):
+            if _not0(d, "RMT_FREQ", "0") or _not0(d, "RMT_FREQ_NP", "0"):
+                raise ValueError("RMT_FREQ / RMT_FREQ_NP: only together with RMT_SENS=1 and RMT_FREQ=1 (n2.freq_plan)")
+            template = _cut(template, FREQ_MARKS)
         if not _is1(d, "RMT_CAMPAIGN"):
             if _not0(d, "RMT_CAMPAIGN_POLICY", "0"):
                 raise ValueError("RMT_CAMPAIGN_POLICY: only together with RMT_CAMPAIGN=1 (n2.campaign_policy_plan)")
@@ -416,6 +424,9 @@ CAMPAIGN_MARKS = ("//>>> RMT_CAMPAIGN", "//<<< RMT_CAMPAIGN\n")
 SENS_MARKS = ("//>>> RMT_SENS", "//<<< RMT_SENS\n")
 
 
+FREQ_MARKS = ("//>>> RMT_FREQ", "//<<< RMT_FREQ\n")        # (inside SENS_MARKS: cutting those takes this text along)
+
+
 def _cut(template, marks):
     """The template without the text from the opening mark to the end of the closing one; a template that has no such
     text comes back as it is."""
@@ -428,7 +439,8 @@ def _cut(template, marks):
 def without_campaign(template):
     """The device template of an ordinary unit: without the text of the files that go into one unit each -
     csrc/kernels/72_campaign.inc and csrc/kernels/73_sensitivity.inc, each from its opening mark to the end of its closing
-    one; a template that has no such text comes back as it is."""
+    one (the sensitivity sweep's closes behind csrc/kernels/74_frequency.inc, whose text goes with it); a template that
+    has no such text comes back as it is."""
     return _cut(_cut(template, SENS_MARKS), CAMPAIGN_MARKS)
 
 

@@ -32,6 +32,8 @@ def rmtExe(modelInput):
                              "model 'N2' (got model %r)" % (modelType,))
         from .sensitivity import check_model as check_sensitivity
         check_sensitivity(modelInput)         # solver-config 'sensitivity': model N2 only (needs 'initial': asked first)
+        from .frequency import check_model as check_frequency
+        check_frequency(modelInput)           # solver-config 'frequency-response': model N2 only
         from .monitor import check_model
         check_model(modelInput)               # solver-config 'monitor': models N2 and M2 only
         from .control import check_model as check_control

@@ -5,14 +5,14 @@ Runs only in the build container, where /root/reference exists:
 
     PYTHONPATH=/root/reference MPLBACKEND=Agg python3 tools/make_golden.py <what> [...]
 
-<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign policy sensitivity fit  (see
+<what> in: setup rhs rk4 tight=<case> default=<case> multistep n1 helpers plot m2 m2run setting m7 m1 schedule feed control steady profile campaign policy sensitivity fit frequency  (see
 SURVEY.md section 8(c), G1..G7; m7 / m1: the steady models, G12; schedule[=probes|A|A1|B|C|D]: time-varying inlet and
 coolant conditions, G13; feed[=probes|FA|FA1|FB|FC|FD]: time-varying feed composition, G14; control[=json|CA|CB|CC|CD]:
 closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|syn12]: discrete steady states of model N2,
 G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18; campaign[=DA|DB|DC|DI]:
 time-on-stream runs with catalyst deactivation, G19; policy[=PA|PS|PB]: the coolant policy of such a run, G20;
 sensitivity[=SA|SB|SK|SW]: parametric sensitivities of the steady state, G21; fit[=FA|FB|FN]: kinetic parameter
-estimation from steady-state data, G22 - like G13..G15 these
+estimation from steady-state data, G22; frequency[=FA|FB|FI]: frequency response of the steady state, G23 - like G13..G15 these
 run SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
@@ -1597,6 +1597,54 @@ def g_fit(which=None):
               % (name, time.time() - t0, out["p_ref"], out["cost"], out["cond"], out["residual_gate"]), flush=True)
 
 
+# ------------------------------------------------------------------ G23: frequency response of the N2 operating point
+# (solver-config "frequency-response", rmt_app_amd/frequency.py).  tests/freq_ref.py: the dense Jacobian, input columns and
+# output map of the oracle's right-hand side around its steady state by Richardson-extrapolated central differences,
+# G(iw) = R_y (iwI - J)^-1 B + R_p by LAPACK; nothing of the product is imported.  A case is refused (SystemExit) when
+# fd_error exceeds sens_ref.FD_CAP of a row's largest magnitude, when the steady state misses the gate, when a species is
+# within 10 differencing steps of the clamp, or (FA) when G(0) differs from G21's D of case SA by more than the two fd_errors.
+def g_frequency(which=None):
+    import freq_ref as FQ
+    import sens_ref as SR
+    from oracle import n2_oracle as O
+    path = os.path.join(GOLD, "g23_frequency.json")
+    meta = {"cases": {}, "gate": SR.CR.GATE, "fd_cap": SR.FD_CAP, "delta": FQ.DELTA0,
+            "reference": "dense J, B and the output map of oracle.n2_oracle.make_rhs_vec (bed A: profile_ref.profiled_rhs) "
+                         "around its steady state by central differences at d and d/2 with Richardson; G(iw) = R_y (iwI - "
+                         "J)^-1 B + R_p by LAPACK; fd_error = max|G(d/2) - G(d)| per (input, row) (tests/freq_ref.py)"}
+    for name in ([which] if which else list(FQ.CASES)):
+        t0 = time.time()
+        out = FQ.run_case(O, INP, name, log=lambda msg: print("G23 %s" % msg, flush=True))
+        bad = FQ.refused(out)
+        if bad:
+            raise SystemExit("G23 %s: fd_error exceeds %.0e of the row's largest magnitude in (input, row) %s - not written"
+                             % (name, SR.FD_CAP, bad))
+        if name == "FA":          # the same bed and inputs as G21's SA: G(0) is its D
+            sa = SR.golden("SA")
+            diff = np.max(np.abs(out["G"][:, 0] - sa["D"]), axis=2)
+            if not np.all(diff <= out["fd_error"] + sa["fd_error"]):
+                raise SystemExit("G23 FA: G(0) differs from G21 SA by more than the two fd_errors: %s"
+                                 % (diff/(out["fd_error"] + sa["fd_error"])))
+            print("G23 FA: G(0) against G21 SA, largest part of the two fd_errors: %.3f"
+                  % float(np.max(diff/(out["fd_error"] + sa["fd_error"]))), flush=True)
+        np.savez_compressed(os.path.join(GOLD, "g23_frequency_%s.npz" % name), state=out["state"], rows=out["rows"],
+                            values=out["values"], frequencies=out["frequencies"], G=out["G"], fd_error=out["fd_error"])
+        if os.path.exists(path):
+            with open(path) as fh:
+                meta["cases"] = json.load(fh)["cases"]
+        mag = np.max(np.abs(out["G"]), axis=(1, 3))
+        rel = np.where(mag > 0, out["fd_error"]/np.where(mag > 0, mag, 1.0), 0.0)
+        meta["cases"][name] = dict(FQ.CASES[name], labels=[SR.label(p) for p in FQ.CASES[name]["inputs"]],
+                                   values=[float(v) for v in out["values"]],
+                                   frequencies=[float(v) for v in out["frequencies"]], residual=float(out["residual"]),
+                                   fd_error_relative=float(rel.max()), slowest_rate=float(out["slowest"]),
+                                   convective_rate=float(out["convective"]), largest_real_part=float(out["max_real"]))
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+        print("G23 %s written (%.0f s): worst fd_error / max|row| %.2e, max|f| %.2e"
+              % (name, time.time() - t0, rel.max(), out["residual"]), flush=True)
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1642,6 +1690,8 @@ def main(argv):
             g_sensitivity(what.split("=", 1)[1] if "=" in what else None)
         elif what == "fit" or what.startswith("fit="):
             g_fit(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "frequency" or what.startswith("frequency="):
+            g_frequency(what.split("=", 1)[1] if "=" in what else None)
         elif what.startswith("m2run"):
             kw = dict(a.split("=") for a in what.split(":")[1:])
             g_m2_run(int(kw.get("zNo", 20)), int(kw.get("tNo", 2)), float(kw.get("rtol", 1e-10)),

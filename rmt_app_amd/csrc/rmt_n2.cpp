@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -57,6 +58,36 @@ static int fail(const char* fmt, ...) {
         if (e_ != hipSuccess) return fail("%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
+// One device allocation and its size, freed with its owner.  reserve() is THE grow rule of every buffer that is created
+// on first use or grows with a call: large enough - nothing; else wait for the stream (a launch in flight may still use
+// the old buffer), free, allocate; a failure leaves the buffer empty.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    int reserve(hipStream_t stream, size_t need) {
+        if (bytes >= need) return 0;
+        if (p) {
+            HIP_OK(hipStreamSynchronize(stream));
+            release();
+        }
+        HIP_OK(hipMalloc(&p, need));
+        bytes = need;
+        return 0;
+    }
+    template <class T>
+    T* as() const { return (T*)p; }
+};
+
+// (Kernel arguments name a buffer as `&buf.p`: the address of the device pointer, read at the launch.)
 struct rmt_n2_handle {
     int S = 0, V = 0, NU = 0, N = 0, E = 0, fp32 = 0, block = 0, npt = 0, mode = 0, device = 0;
     int ros_nb = 0;                          // mesh nodes per workgroup of the stiff stepper (block, or block / 4 in the quad layout)
@@ -66,21 +97,18 @@ struct rmt_n2_handle {
                   f_rk45_mem = nullptr, f_multistep = nullptr, f_rk4_chain = nullptr, f_ros4 = nullptr, f_n1 = nullptr,
                   f_ros4_chain = nullptr, f_rk45_chain = nullptr, f_rk4_redo = nullptr, f_rk4_chain_redo = nullptr,
                   f_march = nullptr, f_campaign = nullptr, f_policy = nullptr, f_sens = nullptr, f_freq = nullptr;
-    unsigned long long* d_rings = nullptr;   // tagged-word links of the chained stiff stepper: rings, decision slots, abort words
-    size_t ring_bytes = 0;
-    double* d_members1 = nullptr;
-    unsigned* d_mask = nullptr;
-    size_t mask_elems = 0;
-    unsigned long long* d_sync = nullptr;
-    double* d_slots = nullptr;
-    size_t chain_links = 0;
     int n_cus = 0;
-    double* d_members = nullptr;
-    unsigned* d_flags = nullptr;
-    void* d_work = nullptr;
-    void* d_backup = nullptr;          // chained cached RK4 stepper: the launch's input, and its redo / status words
-    unsigned* d_redo = nullptr;
-    size_t work_bytes = 0;
+    DevBuf members;                          // the member rows [E][RMT_N2_MEMBER_FIXED + S + NU]
+    // one status word per reactor + one word behind them: how many reactor-launches the cached RK4 steppers handed to
+    // their plain twins so far (rmt_n2_fallbacks)
+    // (a second word behind them: non-zero = rmt_n2_rk4_reg_redo integrates EVERY reactor, the cached stepper is skipped)
+    DevBuf flags;
+    DevBuf work;                             // stage arrays of the memory-resident steppers, in states [E][V][N]
+    DevBuf mask;                             // one word per node of the one-workgroup stiff stepper
+    DevBuf rings;                            // tagged-word links of the chained steppers: rings, decision slots, abort words
+    DevBuf sync, slots;                      // chained RK4 stepper: 32 words and 8 (V + 1) doubles per link
+    DevBuf backup, redo;                     // chained cached RK4 stepper: the launch's input, and its redo / status words
+    DevBuf members1;                         // the rows of rmt_n1_profile
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // cached one-workgroup RK4 stepper: the fallback counter is copied back behind every cached launch (pinned word +
@@ -95,26 +123,38 @@ struct rmt_n2_handle {
     int last_chunks = 1, last_teams = 0;     // geometry of the last stepper launch (rmt_n2_last_geometry)
     // axial profiles (code objects generated with RMT_PROFILE): the table [E][2][N] and the module's pointer to it
     int profiled = 0;
-    double* d_profile = nullptr;
+    DevBuf profile;
     hipDeviceptr_t profile_slot = nullptr;   // address of the module's `rmt_profile_tab`
-    double* d_law = nullptr;                 // campaign units (RMT_CAMPAIGN): the deactivation law rows [E][5]
+    DevBuf law;                              // campaign units (RMT_CAMPAIGN): the deactivation law rows [E][5]
     // policy units (RMT_CAMPAIGN_POLICY): the rows [E][4] = {target, lo, hi, tolerance} with the carried coolant levels [E]
     // behind them in ONE allocation, and the index of the held component
-    double* d_policy = nullptr;
+    DevBuf policy;
     int policy_comp = -1;
+
+    unsigned* status_words() const { return flags.as<unsigned>(); }
+    // Runs on the handle's device (rmt_n2_destroy switches to it; rmt_n2_create has not left it); the buffers go after it.
+    ~rmt_n2_handle() {
+        if (fb_pending && ev_fb) (void)hipEventSynchronize(ev_fb);       // the counter copy into fb_host has landed
+        if (ev_fb) (void)hipEventDestroy(ev_fb);
+        if (fb_host) (void)hipHostFree(fb_host);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (module) (void)hipModuleUnload(module);
+    }
 };
 
 // a profiled handle launches nothing before its table is there (the kernels would read through a null pointer)
-#define PROFILE_READY(h)                                                                    \
-    do {                                                                                    \
-        if ((h)->profiled && !(h)->d_profile)                                               \
-            return fail("this handle's code object was generated with RMT_PROFILE: call rmt_n2_set_profile before the "  \
-                        "first launch");                                                    \
-    } while (0)
+static int profile_missing(const rmt_n2_handle* h) {
+    if (h->profiled && !h->profile.p)
+        return fail("this handle's code object was generated with RMT_PROFILE: call rmt_n2_set_profile before the "
+                    "first launch");
+    return 0;
+}
 
-// bytes of the member rows [E][RMT_N2_MEMBER_FIXED + S + NU] and of one state [E][V][N]
+// bytes of the member rows [E][RMT_N2_MEMBER_FIXED + S + NU], of one state [E][V][N] and of the profile table [E][2][N]
 static size_t member_bytes(const rmt_n2_handle* h) { return (size_t)h->E * (RMT_N2_MEMBER_FIXED + h->S + h->NU) * sizeof(double); }
 static size_t state_bytes(const rmt_n2_handle* h) { return (size_t)h->E * h->V * h->N * h->real_size; }
+static size_t profile_bytes(const rmt_n2_handle* h) { return (size_t)h->E * 2 * (size_t)h->N * sizeof(double); }
 
 // Every entry point runs on the device the handle was created on: workspace allocations, event
 // records and module launches all act on the CURRENT device, which the caller may have changed
@@ -232,7 +272,8 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail("no HIP device available: the N2 integrator has no CPU fallback");
-    rmt_n2_handle* h = new rmt_n2_handle();
+    std::unique_ptr<rmt_n2_handle> owner(new rmt_n2_handle());       // (every failing exit below releases what exists so far)
+    rmt_n2_handle* h = owner.get();
     h->S = p->n_species;
     h->V = p->n_vars;
     h->NU = p->n_user_params;
@@ -244,17 +285,8 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
     h->npt = p->nodes_per_thread;
     h->real_size = p->fp32 ? 4 : 8;
     h->profiled = p->profiled;
-#define CREATE_OK(call)                                                                     \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            fail("%s failed: %s", #call, hipGetErrorString(e_));                            \
-            rmt_n2_destroy(h);                                                              \
-            return 1;                                                                       \
-        }                                                                                   \
-    } while (0)
-    CREATE_OK(hipGetDevice(&h->device));
-    CREATE_OK(hipModuleLoadData(&h->module, p->code_object));
+    HIP_OK(hipGetDevice(&h->device));
+    HIP_OK(hipModuleLoadData(&h->module, p->code_object));
     // The kernels of the code object; the optional ones depend on what it was generated with.  rmt_n2_rk4_reg_redo /
     // rmt_n2_rk4_chain_redo: code objects whose RK4 stepper caches the temperature-only rate constants (RMT_KCACHE) carry
     // the plain stepper as a second kernel - it re-integrates the reactors the cached one gave up on.
@@ -282,63 +314,33 @@ extern "C" int rmt_n2_create(const rmt_n2_plan* p, rmt_n2_handle** out) {
         const hipError_t e = hipModuleGetFunction(&(h->*k.f), h->module, k.name);
         if (e == hipSuccess) continue;
         h->*k.f = nullptr;
-        if (!k.required) continue;
-        fail("hipModuleGetFunction(\"%s\") failed: %s", k.name, hipGetErrorString(e));
-        rmt_n2_destroy(h);
-        return 1;
+        if (k.required) return fail("hipModuleGetFunction(\"%s\") failed: %s", k.name, hipGetErrorString(e));
     }
     (void)hipGetLastError();
     if (h->profiled) {
         size_t bytes = 0;
         const hipError_t e = hipModuleGetGlobal(&h->profile_slot, &bytes, h->module, "rmt_profile_tab");
-        if (e != hipSuccess || bytes != sizeof(double*)) {
-            fail("plan.profiled = 1, but the code object has no rmt_profile_tab (generate it with RMT_PROFILE 1): %s",
-                 hipGetErrorString(e));
-            rmt_n2_destroy(h);
-            return 1;
-        }
+        if (e != hipSuccess || bytes != sizeof(double*))
+            return fail("plan.profiled = 1, but the code object has no rmt_profile_tab (generate it with RMT_PROFILE 1): %s",
+                        hipGetErrorString(e));
     }
-    CREATE_OK(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    const size_t mbytes = member_bytes(h);
-    CREATE_OK(hipMalloc((void**)&h->d_members, mbytes));
-    CREATE_OK(hipMemcpy(h->d_members, p->members, mbytes, hipMemcpyHostToDevice));
-    // one status word per reactor + one word behind them: how many reactor-launches the cached RK4 steppers handed to
-    // their plain twins so far (rmt_n2_fallbacks)
-    // (a second word behind them: non-zero = rmt_n2_rk4_reg_redo integrates EVERY reactor, the cached stepper is skipped)
-    CREATE_OK(hipMalloc((void**)&h->d_flags, ((size_t)h->E + 2) * sizeof(unsigned)));
-    CREATE_OK(hipMemset(h->d_flags, 0, ((size_t)h->E + 2) * sizeof(unsigned)));
-    CREATE_OK(hipHostMalloc((void**)&h->fb_host, 2 * sizeof(unsigned), hipHostMallocDefault));
+    HIP_OK(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    if (h->members.reserve(nullptr, member_bytes(h))) return 1;
+    HIP_OK(hipMemcpy(h->members.p, p->members, member_bytes(h), hipMemcpyHostToDevice));
+    if (h->flags.reserve(nullptr, ((size_t)h->E + 2) * sizeof(unsigned))) return 1;
+    HIP_OK(hipMemset(h->flags.p, 0, h->flags.bytes));
+    HIP_OK(hipHostMalloc((void**)&h->fb_host, 2 * sizeof(unsigned), hipHostMallocDefault));
     h->fb_host[0] = h->fb_host[1] = 0u;
-    CREATE_OK(hipEventCreateWithFlags(&h->ev_fb, hipEventDisableTiming));
-    CREATE_OK(hipEventCreate(&h->ev0));
-    CREATE_OK(hipEventCreate(&h->ev1));
-#undef CREATE_OK
-    *out = h;
+    HIP_OK(hipEventCreateWithFlags(&h->ev_fb, hipEventDisableTiming));
+    HIP_OK(hipEventCreate(&h->ev0));
+    HIP_OK(hipEventCreate(&h->ev1));
+    *out = owner.release();
     return 0;
 }
 
 extern "C" void rmt_n2_destroy(rmt_n2_handle* h) {
     if (!h) return;
-    DeviceGuard guard_(h);
-    if (h->fb_pending && h->ev_fb) (void)hipEventSynchronize(h->ev_fb);       // the counter copy into fb_host has landed
-    if (h->d_members) (void)hipFree(h->d_members);
-    if (h->d_profile) (void)hipFree(h->d_profile);
-    if (h->d_law) (void)hipFree(h->d_law);
-    if (h->d_policy) (void)hipFree(h->d_policy);
-    if (h->d_flags) (void)hipFree(h->d_flags);
-    if (h->d_work) (void)hipFree(h->d_work);
-    if (h->d_backup) (void)hipFree(h->d_backup);
-    if (h->d_redo) (void)hipFree(h->d_redo);
-    if (h->d_mask) (void)hipFree(h->d_mask);
-    if (h->d_members1) (void)hipFree(h->d_members1);
-    if (h->d_sync) (void)hipFree(h->d_sync);
-    if (h->d_slots) (void)hipFree(h->d_slots);
-    if (h->d_rings) (void)hipFree(h->d_rings);
-    if (h->ev_fb) (void)hipEventDestroy(h->ev_fb);
-    if (h->fb_host) (void)hipHostFree(h->fb_host);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->module) (void)hipModuleUnload(h->module);
+    DeviceGuard guard_(h->device);
     delete h;
 }
 
@@ -355,30 +357,49 @@ extern "C" int rmt_n2_set_mode(rmt_n2_handle* h, int mode) {
     return 0;
 }
 
-extern "C" int rmt_n2_set_members(rmt_n2_handle* h, const double* members) {
+// new member rows, queued on the stream; `wait`: and the stream synchronised (the host array may be reused)
+static int upload_members(rmt_n2_handle* h, const double* members, bool wait) {
     if (!h || !members) return fail("null argument");
     ON_DEVICE(h);
-    const size_t mbytes = member_bytes(h);
-    HIP_OK(hipMemcpyAsync(h->d_members, members, mbytes, hipMemcpyHostToDevice, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
+    HIP_OK(hipMemcpyAsync(h->members.p, members, member_bytes(h), hipMemcpyHostToDevice, h->stream));
+    if (wait) HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
-extern "C" int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members) {
-    if (!h || !members) return fail("null argument");
-    ON_DEVICE(h);
-    const size_t mbytes = member_bytes(h);
-    HIP_OK(hipMemcpyAsync(h->d_members, members, mbytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-}
+extern "C" int rmt_n2_set_members(rmt_n2_handle* h, const double* members) { return upload_members(h, members, true); }
+extern "C" int rmt_n2_set_members_async(rmt_n2_handle* h, const double* members) { return upload_members(h, members, false); }
 
 extern "C" int rmt_n2_get_members(rmt_n2_handle* h, double* members) {
     if (!h || !members) return fail("null argument");
     ON_DEVICE(h);
-    const size_t mbytes = member_bytes(h);
-    HIP_OK(hipMemcpyAsync(members, h->d_members, mbytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemcpyAsync(members, h->members.p, member_bytes(h), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// THE upload of a table the kernels read through the handle (profile, deactivation law, policy rows + levels): wait for
+// the stream (a launch in flight may still read the old values), allocate on first use, then one blocking copy per part
+// into the same buffer; with `slot` (the module's pointer to the table) that pointer is written and the device
+// synchronised.  A handle whose FIRST upload failed keeps no buffer.
+struct TablePart { const void* src; size_t bytes; };
+static int upload_table(rmt_n2_handle* h, DevBuf* table, const char* who, std::initializer_list<TablePart> parts,
+                        hipDeviceptr_t slot = nullptr) {
+    size_t bytes = 0;
+    for (const TablePart& part : parts) bytes += part.bytes;
+    HIP_OK(hipStreamSynchronize(h->stream));
+    const bool first = !table->p;
+    if (table->reserve(h->stream, bytes)) return 1;
+    hipError_t e = hipSuccess;
+    size_t at = 0;
+    for (const TablePart& part : parts) {
+        if (e == hipSuccess) e = hipMemcpy(table->as<char>() + at, part.src, part.bytes, hipMemcpyHostToDevice);
+        at += part.bytes;
+    }
+    if (e == hipSuccess && slot) e = hipMemcpyHtoD(slot, &table->p, sizeof table->p);
+    if (e == hipSuccess && slot) e = hipDeviceSynchronize();
+    if (e == hipSuccess) return 0;
+    if (first) table->release();
+    return fail("%s: %s", who, hipGetErrorString(e));
 }
 
 extern "C" int rmt_n2_set_profile(rmt_n2_handle* h, const double* table_host) {
@@ -386,76 +407,71 @@ extern "C" int rmt_n2_set_profile(rmt_n2_handle* h, const double* table_host) {
     if (!h->profiled)
         return fail("rmt_n2_set_profile: this handle's code object was not generated with RMT_PROFILE (plan.profiled = 0)");
     ON_DEVICE(h);
-    const size_t bytes = (size_t)h->E * 2 * (size_t)h->N * sizeof(double);
-    // (a launch in flight may still read the old values: wait for it, then ONE blocking upload into the same buffer)
-    HIP_OK(hipStreamSynchronize(h->stream));
-    double* buf = h->d_profile;
-    if (!buf) HIP_OK(hipMalloc((void**)&buf, bytes));
-    hipError_t e = hipMemcpy(buf, table_host, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpyHtoD(h->profile_slot, &buf, sizeof buf);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        if (!h->d_profile) (void)hipFree(buf);
-        return fail("rmt_n2_set_profile: %s", hipGetErrorString(e));
-    }
-    h->d_profile = buf;
-    return 0;
+    return upload_table(h, &h->profile, "rmt_n2_set_profile", {{table_host, profile_bytes(h)}}, h->profile_slot);
 }
 
-static int ensure_work(rmt_n2_handle* h, size_t arrays, size_t extra_bytes = 0) {
-    const size_t need = arrays * state_bytes(h) + extra_bytes;
-    if (h->work_bytes >= need) return 0;
-    if (h->d_work) {
-        HIP_OK(hipStreamSynchronize(h->stream));
-        HIP_OK(hipFree(h->d_work));
-        h->d_work = nullptr;
-        h->work_bytes = 0;
-    }
-    HIP_OK(hipMalloc(&h->d_work, need));
-    h->work_bytes = need;
-    return 0;
+static int reserve_work(rmt_n2_handle* h, size_t arrays) { return h->work.reserve(h->stream, arrays * state_bytes(h)); }
+
+// Reactors longer than one workgroup holds: C chunks of `width` nodes per reactor on C CUs, T teams, every workgroup
+// resident (T*C <= #CUs).  ok: the device (and `limit`, the most chunks the kernel's links allow) admits that chain.
+struct Chain { int C, T; bool ok; };
+static Chain chain_geometry(const rmt_n2_handle* h, int width, int limit) {
+    Chain g;
+    g.C = (h->N + width - 1) / width;
+    g.ok = g.C >= 2 && g.C <= h->n_cus && g.C <= limit;
+    g.T = h->n_cus / g.C;
+    if (g.T > h->E) g.T = h->E;
+    return g;
 }
 
 // tagged-word links of the chained steppers: [links] rings of RMT_N2_RING entries of 2(V+1) words, then 2 decision
 // words and one abort word per team; cleared before every launch (tag 0 never matches)
-static int ensure_rings(rmt_n2_handle* h, int T, int C, unsigned long long** decision, unsigned** abort_words) {
+static int ensure_rings(rmt_n2_handle* h, const Chain& g, unsigned long long** decision, unsigned** abort_words) {
     const size_t words = 2 * (size_t)(h->V + 1);
-    const size_t ring_words = (size_t)T * C * RMT_N2_RING * words;
-    const size_t need = (ring_words + 2 * (size_t)T) * sizeof(unsigned long long) + (size_t)T * sizeof(unsigned);
-    if (h->ring_bytes < need) {
-        if (h->d_rings) { HIP_OK(hipStreamSynchronize(h->stream)); HIP_OK(hipFree(h->d_rings)); }
-        h->d_rings = nullptr; h->ring_bytes = 0;
-        HIP_OK(hipMalloc((void**)&h->d_rings, need));
-        h->ring_bytes = need;
-    }
-    HIP_OK(hipMemsetAsync(h->d_rings, 0, need, h->stream));
-    *decision = h->d_rings + ring_words;
-    *abort_words = (unsigned*)(*decision + 2 * (size_t)T);
+    const size_t ring_words = (size_t)g.T * g.C * RMT_N2_RING * words;
+    const size_t need = (ring_words + 2 * (size_t)g.T) * sizeof(unsigned long long) + (size_t)g.T * sizeof(unsigned);
+    if (h->rings.reserve(h->stream, need)) return 1;
+    HIP_OK(hipMemsetAsync(h->rings.p, 0, need, h->stream));
+    *decision = h->rings.as<unsigned long long>() + ring_words;
+    *abort_words = (unsigned*)(*decision + 2 * (size_t)g.T);
     return 0;
 }
 
-static int launch(rmt_n2_handle* h, hipFunction_t f, void** args, int grid = -1, int chunks = 1, int teams = 0,
-                  hipFunction_t then = nullptr) {
+// THE kernel launch: function, grid, block and arguments
+static int launch(hipStream_t stream, hipFunction_t f, size_t grid, int block, void** args) {
+    HIP_OK(hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, 0, stream, args, nullptr));
+    return 0;
+}
+
+// THE timed bracket of a handle (rmt_n2_last_kernel_ms): ev0, whatever `launches` queues, ev1
+template <class Launches>
+static int timed_region(rmt_n2_handle* h, Launches launches) {
+    HIP_OK(hipEventRecord(h->ev0, h->stream));
+    if (launches()) return 1;
+    HIP_OK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return 0;
+}
+
+// The launch of a stepper (or of the RHS kernel) at the handle's block size, timed and noted for rmt_n2_last_geometry:
+// `teams` teams of `chunks` workgroups each - 0 teams: one workgroup per reactor, or `grid` of them walking the reactors.
+// Several kernels: one behind the other with the same arguments and geometry, inside one bracket.
+static int launch_stepper(rmt_n2_handle* h, std::initializer_list<hipFunction_t> kernels, void** args, int chunks = 1,
+                          int teams = 0, size_t grid = 0) {
     h->last_chunks = chunks;
     h->last_teams = teams > 0 ? teams : h->E;
-    HIP_OK(hipEventRecord(h->ev0, h->stream));
-    HIP_OK(hipModuleLaunchKernel(f, (unsigned)(grid > 0 ? grid : h->E), 1, 1, (unsigned)h->block, 1, 1, 0,
-                                 h->stream, args, nullptr));
-    if (then)          // a follow-up kernel with the same arguments and geometry, inside the timed region
-        HIP_OK(hipModuleLaunchKernel(then, (unsigned)(grid > 0 ? grid : h->E), 1, 1, (unsigned)h->block, 1, 1, 0,
-                                     h->stream, args, nullptr));
-    HIP_OK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    if (!grid) grid = teams > 0 ? (size_t)teams * chunks : (size_t)h->E;
+    return timed_region(h, [&]() -> int {
+        for (hipFunction_t f : kernels)
+            if (launch(h->stream, f, grid, h->block, args)) return 1;
+        return 0;
+    });
 }
 
-// one reactor per lane, one wave per workgroup: the N1 kernel and the per-lane marches (kernels/71 .. 73)
-static int launch_lanes(rmt_n2_handle* h, hipFunction_t f, void** args) {
-    HIP_OK(hipEventRecord(h->ev0, h->stream));
-    HIP_OK(hipModuleLaunchKernel(f, (unsigned)((h->E + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-    HIP_OK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+// one lane per reactor (or per `lanes` of another count), one wave per workgroup: the N1 kernel and the per-lane marches
+// (kernels/71 .. 74); the stepper geometry stays what it was
+static int launch_lanes(rmt_n2_handle* h, hipFunction_t f, void** args, size_t lanes = 0) {
+    return timed_region(h, [&] { return launch(h->stream, f, ((lanes ? lanes : (size_t)h->E) + 63) / 64, 64, args); });
 }
 
 extern "C" int rmt_n2_last_geometry(rmt_n2_handle* h, int* chunks, int* teams) {
@@ -477,10 +493,10 @@ extern "C" int rmt_n2_last_kernel_ms(rmt_n2_handle* h, float* ms) {
 extern "C" int rmt_n2_rhs(rmt_n2_handle* h, double t, const void* y, void* dydt) {
     (void)t; /* the N2 right-hand side is autonomous (pbHomoReactor.py:3706: t unused) */
     if (!h || !y || !dydt) return fail("null argument");
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
     int N = h->N, E = h->E;
-    void* args[] = {(void*)&y, (void*)&dydt, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&h->d_flags};
+    void* args[] = {(void*)&y, (void*)&dydt, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&h->flags.p};
     // persistent workgroups: at most RMT_N2_RHS_WGS_PER_CU per CU, each walking reactors e, e + grid, ...
     static const int per_cu = [] {               // tuning override, read once
         const char* v = getenv("RMT_N2_RHS_WGS_PER_CU");
@@ -488,7 +504,7 @@ extern "C" int rmt_n2_rhs(rmt_n2_handle* h, double t, const void* y, void* dydt)
         return n > 0 ? n : RMT_N2_RHS_WGS_PER_CU;
     }();
     const long long cap = (long long)h->n_cus * per_cu;
-    return launch(h, h->f_rhs, args, h->E < cap ? h->E : (int)cap);
+    return launch_stepper(h, {h->f_rhs}, args, 1, 0, h->E < cap ? (size_t)h->E : (size_t)cap);
 }
 
 static bool fits_registers(const rmt_n2_handle* h) { return h->N <= h->block * h->npt; }
@@ -511,7 +527,7 @@ static bool plain_this_call(rmt_n2_handle* h) {
 
 static int copy_back_fallbacks(rmt_n2_handle* h) {
     if (h->fb_pending) return 0;
-    HIP_OK(hipMemcpyAsync(h->fb_host, h->d_flags + h->E, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemcpyAsync(h->fb_host, h->status_words() + h->E, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipEventRecord(h->ev_fb, h->stream));
     h->fb_pending = true;
     return 0;
@@ -526,7 +542,7 @@ extern "C" int rmt_n2_rk4(rmt_n2_handle* h, void* y, double t0, double dt, int64
     (void)t0;
     if (!h || !y) return fail("null argument");
     if (!(dt > 0) || nsteps < 0) return fail("rk4 needs dt > 0 and nsteps >= 0");
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     long long ns = (long long)nsteps;
@@ -535,88 +551,77 @@ extern "C" int rmt_n2_rk4(rmt_n2_handle* h, void* y, double t0, double dt, int64
         if (!fits_registers(h))
             return fail("register-resident stepper holds at most %d nodes per reactor (N=%d)",
                         h->block * h->npt, h->N);
-        void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&dt, (void*)&ns,
-                        (void*)&h->d_flags};
-        if (!h->f_rk4_redo) return launch(h, h->f_rk4_reg, args);
+        void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&dt, (void*)&ns,
+                        (void*)&h->flags.p};
+        if (!h->f_rk4_redo) return launch_stepper(h, {h->f_rk4_reg}, args);
         // (a stream that is being captured into a graph gets the two kernels and nothing else)
         if (capturing(h)) {
-            HIP_OK(hipModuleLaunchKernel(h->f_rk4_reg, (unsigned)h->E, 1, 1, (unsigned)h->block, 1, 1, 0, h->stream, args, nullptr));
-            HIP_OK(hipModuleLaunchKernel(h->f_rk4_redo, (unsigned)h->E, 1, 1, (unsigned)h->block, 1, 1, 0, h->stream, args, nullptr));
-            return 0;
+            if (launch(h->stream, h->f_rk4_reg, h->E, h->block, args)) return 1;
+            return launch(h->stream, h->f_rk4_redo, h->E, h->block, args);
         }
         if (plain_this_call(h)) {        // flags[E + 1] != 0: rmt_n2_rk4_reg_redo integrates every reactor
-            HIP_OK(hipMemsetAsync(h->d_flags + h->E + 1, 1, sizeof(unsigned), h->stream));
-            const int rc = launch(h, h->f_rk4_redo, args);
-            HIP_OK(hipMemsetAsync(h->d_flags + h->E + 1, 0, sizeof(unsigned), h->stream));
+            HIP_OK(hipMemsetAsync(h->status_words() + h->E + 1, 1, sizeof(unsigned), h->stream));
+            const int rc = launch_stepper(h, {h->f_rk4_redo}, args);
+            HIP_OK(hipMemsetAsync(h->status_words() + h->E + 1, 0, sizeof(unsigned), h->stream));
             return rc;
         }
-        if (launch(h, h->f_rk4_reg, args, -1, 1, 0, h->f_rk4_redo)) return 1;
+        // the cached stepper, and behind it the plain one for the reactors it gave up on
+        if (launch_stepper(h, {h->f_rk4_reg, h->f_rk4_redo}, args)) return 1;
         return copy_back_fallbacks(h);
     }
-    // chained workgroups: C chunks per reactor, T teams, every workgroup resident (T*C <= #CUs)
-    const int W = h->block * h->npt;
-    int C = (h->N + W - 1) / W;
-    const bool can_chain = h->f_rk4_chain && C >= 2 && C <= h->n_cus;
+    const Chain g = chain_geometry(h, h->block * h->npt, h->n_cus);
+    const bool can_chain = h->f_rk4_chain && g.ok;
     if (h->mode == 3 && !can_chain)
-        return fail("chained stepper needs 2 <= chunks (%d) <= CUs (%d)", C, h->n_cus);
+        return fail("chained stepper needs 2 <= chunks (%d) <= CUs (%d)", g.C, h->n_cus);
     if (h->mode == 3 || (h->mode == 0 && can_chain)) {
-        int T = h->n_cus / C;
-        if (T > h->E) T = h->E;
-        const size_t links = (size_t)T * C;
-        if (h->chain_links < links) {
-            if (h->d_sync) { HIP_OK(hipStreamSynchronize(h->stream)); HIP_OK(hipFree(h->d_sync)); HIP_OK(hipFree(h->d_slots)); }
-            h->d_sync = nullptr; h->d_slots = nullptr; h->chain_links = 0;
-            HIP_OK(hipMalloc((void**)&h->d_sync, links * 32 * sizeof(unsigned long long)));
-            HIP_OK(hipMalloc((void**)&h->d_slots, links * 8 * (size_t)(h->V + 1) * sizeof(double)));
-            h->chain_links = links;
-        }
+        int C = g.C, T = g.T;
+        const size_t links = (size_t)T * C, sync_bytes = links * 32 * sizeof(unsigned long long);
+        if (h->sync.reserve(h->stream, sync_bytes)) return 1;
+        if (h->slots.reserve(h->stream, links * 8 * (size_t)(h->V + 1) * sizeof(double))) return 1;
         // a chained stepper that caches the temperature-only rate constants (RMT_KCACHE_CHAIN) saves the launch's input
         // and is followed by rmt_n2_rk4_chain_redo on the same grid, see kernels/50_rk4.inc rmt_rk4_chain_body
         void* backup = nullptr;
         unsigned *redo = nullptr, *falt = nullptr;
         if (h->f_rk4_chain_redo) {
-            const size_t state = state_bytes(h);
-            if (!h->d_backup) {
-                HIP_OK(hipMalloc(&h->d_backup, state));
-                HIP_OK(hipMalloc((void**)&h->d_redo, 2 * (size_t)h->E * sizeof(unsigned)));
-            }
-            backup = h->d_backup;
-            redo = h->d_redo;
-            falt = h->d_redo + h->E;
-            HIP_OK(hipMemsetAsync(h->d_redo, 0, 2 * (size_t)h->E * sizeof(unsigned), h->stream));
+            const size_t redo_bytes = 2 * (size_t)h->E * sizeof(unsigned);
+            if (h->backup.reserve(h->stream, state_bytes(h)) || h->redo.reserve(h->stream, redo_bytes)) return 1;
+            backup = h->backup.p;
+            redo = h->redo.as<unsigned>();
+            falt = redo + h->E;
+            HIP_OK(hipMemsetAsync(redo, 0, redo_bytes, h->stream));
         }
         // the same policy as for the one-workgroup stepper: after a launch that lost half of its reactors the plain
         // chained stepper runs alone for a while - every redo word set (to a value the fallback counter does not count),
         // the input copied to the backup buffer the plain stepper reads
         const bool plain = h->f_rk4_chain_redo && !capturing(h) && plain_this_call(h);
         if (plain) {
-            const size_t state = state_bytes(h);
-            HIP_OK(hipMemcpyAsync(h->d_backup, y, state, hipMemcpyDeviceToDevice, h->stream));
-            HIP_OK(hipMemsetAsync(h->d_redo, 2, (size_t)h->E * sizeof(unsigned), h->stream));
+            HIP_OK(hipMemcpyAsync(backup, y, state_bytes(h), hipMemcpyDeviceToDevice, h->stream));
+            HIP_OK(hipMemsetAsync(redo, 2, (size_t)h->E * sizeof(unsigned), h->stream));
         }
         unsigned long long* decision = nullptr;
         unsigned* abort_words = nullptr;
-        void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&C, (void*)&T,
-                        (void*)&dt, (void*)&ns, (void*)&h->d_sync, (void*)&h->d_slots, (void*)&h->d_flags,
-                        (void*)&h->d_rings, (void*)&abort_words, (void*)&backup, (void*)&redo, (void*)&falt};
+        void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&C, (void*)&T,
+                        (void*)&dt, (void*)&ns, (void*)&h->sync.p, (void*)&h->slots.p, (void*)&h->flags.p,
+                        (void*)&h->rings.p, (void*)&abort_words, (void*)&backup, (void*)&redo, (void*)&falt};
         h->last_chunks = C;
         h->last_teams = T;
-        HIP_OK(hipEventRecord(h->ev0, h->stream));
-        for (hipFunction_t f : {plain ? (hipFunction_t) nullptr : h->f_rk4_chain, h->f_rk4_chain_redo}) {
-            if (!f) continue;
-            HIP_OK(hipMemsetAsync(h->d_sync, 0, links * 32 * sizeof(unsigned long long), h->stream));
-            if (ensure_rings(h, T, C, &decision, &abort_words)) return 1;        // (clears the rings)
-            HIP_OK(hipModuleLaunchKernel(f, (unsigned)(T * C), 1, 1, (unsigned)h->block, 1, 1, 0, h->stream, args, nullptr));
-        }
-        HIP_OK(hipEventRecord(h->ev1, h->stream));
-        h->timed = true;
+        const int rc = timed_region(h, [&]() -> int {
+            for (hipFunction_t f : {plain ? (hipFunction_t) nullptr : h->f_rk4_chain, h->f_rk4_chain_redo}) {
+                if (!f) continue;
+                HIP_OK(hipMemsetAsync(h->sync.p, 0, sync_bytes, h->stream));
+                if (ensure_rings(h, g, &decision, &abort_words)) return 1;
+                if (launch(h->stream, f, links, h->block, args)) return 1;
+            }
+            return 0;
+        });
+        if (rc) return rc;
         if (h->f_rk4_chain_redo && !plain && !capturing(h)) return copy_back_fallbacks(h);
         return 0;
     }
-    if (ensure_work(h, 3)) return 1;
-    void* args[] = {(void*)&y, (void*)&h->d_work, (void*)&h->d_members, (void*)&N, (void*)&E,
-                    (void*)&dt, (void*)&ns, (void*)&h->d_flags};
-    return launch(h, h->f_rk4_mem, args);
+    if (reserve_work(h, 3)) return 1;
+    void* args[] = {(void*)&y, (void*)&h->work.p, (void*)&h->members.p, (void*)&N, (void*)&E,
+                    (void*)&dt, (void*)&ns, (void*)&h->flags.p};
+    return launch_stepper(h, {h->f_rk4_mem}, args);
 }
 
 extern "C" int rmt_n2_multistep(rmt_n2_handle* h, void* y, double t0, double dt, int64_t nsteps,
@@ -626,59 +631,55 @@ extern "C" int rmt_n2_multistep(rmt_n2_handle* h, void* y, double t0, double dt,
     if (!(dt > 0) || nsteps < 3) return fail("multistep needs dt > 0 and nsteps >= 3");
     if (method != 0 && method != 1) return fail("method must be 0 (AdBash3) or 1 (PreCorr3)");
     if (!h->f_multistep) return fail("code object has no multistep kernel");
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
-    if (ensure_work(h, 8)) return 1;
+    if (reserve_work(h, 8)) return 1;
     int N = h->N, E = h->E;
     long long ns = (long long)nsteps;
-    void* args[] = {(void*)&y, (void*)&h->d_work, (void*)&h->d_members, (void*)&N, (void*)&E,
-                    (void*)&dt, (void*)&ns, (void*)&method, (void*)&h->d_flags};
-    return launch(h, h->f_multistep, args);
+    void* args[] = {(void*)&y, (void*)&h->work.p, (void*)&h->members.p, (void*)&N, (void*)&E,
+                    (void*)&dt, (void*)&ns, (void*)&method, (void*)&h->flags.p};
+    return launch_stepper(h, {h->f_multistep}, args);
 }
 
 extern "C" int rmt_n2_rk45(rmt_n2_handle* h, void* y, double t0, double t1, double rtol, double atol,
                            double h0, int64_t max_steps, rmt_n2_stats* stats) {
     if (!h || !y || !stats) return fail("null argument");
     if (!(t1 > t0) || !(rtol > 0) || !(atol >= 0) || !(h0 != 0)) return fail("bad rk45 arguments");
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     long long ms = (long long)max_steps;
     const bool reg = (h->mode == 1 || (h->mode == 0 && fits_registers(h))) && h->f_rk45_reg;
     if (reg) {
         if (!fits_registers(h)) return fail("register-resident rk45 does not fit N=%d", h->N);
-        void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&t0, (void*)&t1,
+        void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&t0, (void*)&t1,
                         (void*)&rtol, (void*)&atol, (void*)&h0, (void*)&ms, (void*)&stats,
-                        (void*)&h->d_flags};
-        return launch(h, h->f_rk45_reg, args);
+                        (void*)&h->flags.p};
+        return launch_stepper(h, {h->f_rk45_reg}, args);
     }
-    // Reactors longer than one workgroup's on-chip capacity: C chunks per reactor on C CUs, T teams, every
-    // workgroup resident (rmt_n2_rk45_chain; the code object has it when the on-chip slots fit the geometry).
-    {
-        const int W = h->block * h->npt;
-        int C = (h->N + W - 1) / W;
-        const bool can_chain = h->f_rk45_chain && C >= 2 && C <= h->n_cus && C <= RMT_N2_MAX_CHUNKS;
-        if (h->mode == 3 && !can_chain)
-            return fail("chained rk45 needs the on-chip stepper in the code object and 2 <= chunks (%d) <= %d", C,
-                        h->n_cus < RMT_N2_MAX_CHUNKS ? h->n_cus : RMT_N2_MAX_CHUNKS);
-        if (can_chain && (h->mode == 3 || h->mode == 0)) {
-            int T = h->n_cus / C;
-            if (T > h->E) T = h->E;
-            unsigned long long* decision = nullptr;
-            unsigned* abort_words = nullptr;
-            if (ensure_rings(h, T, C, &decision, &abort_words)) return 1;
-            void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&C, (void*)&T, (void*)&t0,
-                            (void*)&t1, (void*)&rtol, (void*)&atol, (void*)&h0, (void*)&ms, (void*)&stats,
-                            (void*)&h->d_flags, (void*)&h->d_rings, (void*)&decision, (void*)&abort_words};
-            return launch(h, h->f_rk45_chain, args, T * C, C, T);
-        }
+    // Reactors longer than one workgroup's on-chip capacity: rmt_n2_rk45_chain (the code object has it when the on-chip
+    // slots fit the geometry).
+    const Chain g = chain_geometry(h, h->block * h->npt, RMT_N2_MAX_CHUNKS);
+    const bool can_chain = h->f_rk45_chain && g.ok;
+    if (h->mode == 3 && !can_chain)
+        return fail("chained rk45 needs the on-chip stepper in the code object and 2 <= chunks (%d) <= %d", g.C,
+                    h->n_cus < RMT_N2_MAX_CHUNKS ? h->n_cus : RMT_N2_MAX_CHUNKS);
+    if (can_chain && (h->mode == 3 || h->mode == 0)) {
+        int C = g.C, T = g.T;
+        unsigned long long* decision = nullptr;
+        unsigned* abort_words = nullptr;
+        if (ensure_rings(h, g, &decision, &abort_words)) return 1;
+        void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&C, (void*)&T, (void*)&t0,
+                        (void*)&t1, (void*)&rtol, (void*)&atol, (void*)&h0, (void*)&ms, (void*)&stats,
+                        (void*)&h->flags.p, (void*)&h->rings.p, (void*)&decision, (void*)&abort_words};
+        return launch_stepper(h, {h->f_rk45_chain}, args, C, T);
     }
     if (!h->f_rk45_mem) return fail("code object has no rk45 kernel");
-    if (ensure_work(h, 10)) return 1;      // K_1..K_7 (when they do not fit in LDS), y_new, K_1/K_7 of the FSAL swap
-    void* args[] = {(void*)&y, (void*)&h->d_work, (void*)&h->d_members, (void*)&N, (void*)&E,
+    if (reserve_work(h, 10)) return 1;     // K_1..K_7 (when they do not fit in LDS), y_new, K_1/K_7 of the FSAL swap
+    void* args[] = {(void*)&y, (void*)&h->work.p, (void*)&h->members.p, (void*)&N, (void*)&E,
                     (void*)&t0, (void*)&t1, (void*)&rtol, (void*)&atol, (void*)&h0, (void*)&ms,
-                    (void*)&stats, (void*)&h->d_flags};
-    return launch(h, h->f_rk45_mem, args);
+                    (void*)&stats, (void*)&h->flags.p};
+    return launch_stepper(h, {h->f_rk45_mem}, args);
 }
 
 extern "C" int rmt_n2_ros4(rmt_n2_handle* h, void* y, double t0, double t1, double rtol, double atol,
@@ -686,7 +687,7 @@ extern "C" int rmt_n2_ros4(rmt_n2_handle* h, void* y, double t0, double t1, doub
     if (!h || !y || !stats) return fail("null argument");
     if (!(t1 > t0) || !(rtol > 0) || !(atol >= 0) || !(h0 != 0)) return fail("bad ros4 arguments");
     if (!h->f_ros4) return fail("code object has no ros4 kernel");
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
     if (h->block > 512)
         return fail("the Rosenbrock kernel holds a VxV matrix per lane: generate the code object with "
@@ -726,38 +727,29 @@ extern "C" int rmt_n2_ros4(rmt_n2_handle* h, void* y, double t0, double t1, doub
     if (h->mode == 3 && C < 2)
         return fail("chained stiff stepper needs >= 2 node blocks per reactor (N=%d block=%d E=%d CUs=%d)",
                     h->N, h->block, h->E, h->n_cus);
-    if (C >= 2) {
-        const int bpc = (nblocks + C - 1) / C;          // node blocks per chunk
-        C = (nblocks + bpc - 1) / bpc;
-        int W = bpc * h->ros_nb;
-        int T = h->n_cus / C;
-        if (T > h->E) T = h->E;
-        if (ensure_work(h, 1)) return 1;                // y_new
-        unsigned long long* decision = nullptr;
-        unsigned* abort_words = nullptr;
-        if (ensure_rings(h, T, C, &decision, &abort_words)) return 1;
-        int N = h->N, E = h->E;
-        long long ms = (long long)max_steps;
-        void* args[] = {(void*)&y, (void*)&h->d_work, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&C, (void*)&T,
-                        (void*)&W, (void*)&t0, (void*)&t1, (void*)&rtol, (void*)&atol, (void*)&h0, (void*)&ms,
-                        (void*)&stats, (void*)&h->d_flags, (void*)&h->d_rings, (void*)&decision, (void*)&abort_words};
-        return launch(h, h->f_ros4_chain, args, T * C, C, T);
-    }
-    // 7 vector arrays + the VxV inverse per node (= V more "vector arrays")
-    if (ensure_work(h, 8 + (size_t)h->V)) return 1;   // 7 stage arrays + VxV inverses + upwind coupling (model M2)
-    const size_t nmask = (size_t)h->E * h->N;
-    if (h->mask_elems < nmask) {
-        if (h->d_mask) { HIP_OK(hipStreamSynchronize(h->stream)); HIP_OK(hipFree(h->d_mask)); }
-        h->d_mask = nullptr; h->mask_elems = 0;
-        HIP_OK(hipMalloc((void**)&h->d_mask, nmask * sizeof(unsigned)));
-        h->mask_elems = nmask;
-    }
     int N = h->N, E = h->E;
     long long ms = (long long)max_steps;
-    void* args[] = {(void*)&y, (void*)&h->d_work, (void*)&h->d_mask, (void*)&h->d_members, (void*)&N,
+    if (C >= 2) {
+        int W = (nblocks + C - 1) / C * h->ros_nb;      // whole node blocks per chunk; the chunks that many nodes make
+        const Chain g = chain_geometry(h, W, RMT_N2_MAX_CHUNKS);
+        int T = g.T;
+        C = g.C;
+        if (reserve_work(h, 1)) return 1;               // y_new
+        unsigned long long* decision = nullptr;
+        unsigned* abort_words = nullptr;
+        if (ensure_rings(h, g, &decision, &abort_words)) return 1;
+        void* args[] = {(void*)&y, (void*)&h->work.p, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&C, (void*)&T,
+                        (void*)&W, (void*)&t0, (void*)&t1, (void*)&rtol, (void*)&atol, (void*)&h0, (void*)&ms,
+                        (void*)&stats, (void*)&h->flags.p, (void*)&h->rings.p, (void*)&decision, (void*)&abort_words};
+        return launch_stepper(h, {h->f_ros4_chain}, args, C, T);
+    }
+    // 7 vector arrays + the VxV inverse per node (= V more "vector arrays")
+    if (reserve_work(h, 8 + (size_t)h->V)) return 1;   // 7 stage arrays + VxV inverses + upwind coupling (model M2)
+    if (h->mask.reserve(h->stream, (size_t)h->E * h->N * sizeof(unsigned))) return 1;
+    void* args[] = {(void*)&y, (void*)&h->work.p, (void*)&h->mask.p, (void*)&h->members.p, (void*)&N,
                     (void*)&E, (void*)&t0, (void*)&t1, (void*)&rtol, (void*)&atol, (void*)&h0,
-                    (void*)&ms, (void*)&stats, (void*)&h->d_flags};
-    return launch(h, h->f_ros4, args);
+                    (void*)&ms, (void*)&stats, (void*)&h->flags.p};
+    return launch_stepper(h, {h->f_ros4}, args);
 }
 
 extern "C" int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* out, int nout, double rtol,
@@ -765,16 +757,15 @@ extern "C" int rmt_n1_profile(rmt_n2_handle* h, const double* members1, void* ou
     if (!h || !members1 || !out || !stats) return fail("null argument");
     if (nout < 2 || !(rtol > 0) || !(atol >= 0) || !(h0 > 0)) return fail("bad N1 arguments");
     if (!h->f_n1) return fail("code object has no N1 kernel");
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
-    const size_t mbytes = member_bytes(h);
-    if (!h->d_members1) HIP_OK(hipMalloc((void**)&h->d_members1, mbytes));
-    HIP_OK(hipMemcpyAsync(h->d_members1, members1, mbytes, hipMemcpyHostToDevice, h->stream));
+    if (h->members1.reserve(h->stream, member_bytes(h))) return 1;
+    HIP_OK(hipMemcpyAsync(h->members1.p, members1, member_bytes(h), hipMemcpyHostToDevice, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     int E = h->E;
     long long ms = (long long)max_steps;
-    void* args[] = {(void*)&h->d_members1, (void*)&out, (void*)&E, (void*)&nout, (void*)&rtol, (void*)&atol,
-                    (void*)&h0, (void*)&ms, (void*)&stats, (void*)&h->d_flags};
+    void* args[] = {(void*)&h->members1.p, (void*)&out, (void*)&E, (void*)&nout, (void*)&rtol, (void*)&atol,
+                    (void*)&h0, (void*)&ms, (void*)&stats, (void*)&h->flags.p};
     return launch_lanes(h, h->f_n1, args);
 }
 
@@ -783,18 +774,38 @@ extern "C" int rmt_n2_steady_march(rmt_n2_handle* h, void* y_out, double tol, in
     if (!(tol > 0) || max_iter < 1) return fail("bad steady-march arguments (tolerance > 0, max_iter >= 1)");
     if (!h->f_march) return fail("code object has no rmt_n2_steady_march (generate it with RMT_WITH_MARCH)");
     if (h->fp32) return fail("the steady-state march is fp64 only");
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     long long mi = (long long)max_iter;
-    void* args[] = {(void*)&y_out, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
-                    (void*)&h->d_flags};
+    void* args[] = {(void*)&y_out, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
+                    (void*)&h->flags.p};
     return launch_lanes(h, h->f_march, args);
 }
 
-// solver-config "sensitivity" (kernels/73_sensitivity.inc): the tangent march over the converged state, behind
-// rmt_n2_steady_march on the same handle.  The descriptor travels by value: {kind[8], index[8]} as the kernel declares it.
+// The descriptor of the sensitivity and the frequency sweep travels by value: {kind[8], index[8]} as the kernels declare
+// it.  ``who``: the entry point, ``what``: "parameter" / "input" (for the error text); kinds 0 TM, 1 THETA_IN, 2 P0,
+// 3 CIN[index] and - where ``max_kind`` is 4 - 4 user column [index].
 #define RMT_N2_SENS_MAX 8
+struct ParamDesc { int kind[RMT_N2_SENS_MAX], index[RMT_N2_SENS_MAX]; };
+static int build_desc(const rmt_n2_handle* h, const char* who, const char* what, int max_kind, int n, const int* kinds,
+                      const int* indices, ParamDesc* desc) {
+    std::memset(desc, 0, sizeof(*desc));
+    const bool user = max_kind >= 4;
+    for (int p = 0; p < n; ++p) {
+        const int k = kinds[p], i = indices[p];
+        if (k < 0 || k > max_kind || i < 0 || (k == 3 && i >= h->S) || (k == 4 && i >= h->NU) || (k < 3 && i != 0))
+            return fail("%s: %s %d: kind %d (0 TM, 1 THETA_IN, 2 P0, 3 CIN[index]%s) with index %d is out of range (S = %d%s)",
+                        who, what, p, k, user ? ", 4 user column [index]" : "", i, h->S,
+                        user ? (", NU = " + std::to_string(h->NU)).c_str() : "");
+        desc->kind[p] = k;
+        desc->index[p] = i;
+    }
+    return 0;
+}
+
+// solver-config "sensitivity" (kernels/73_sensitivity.inc): the tangent march over the converged state, behind
+// rmt_n2_steady_march on the same handle.
 extern "C" int rmt_n2_steady_sens(rmt_n2_handle* h, const void* y, int n_params, const int* kinds, const int* indices,
                                   double* out) {
     if (!h || !y || !kinds || !indices || !out) return fail("rmt_n2_steady_sens: null argument");
@@ -803,27 +814,19 @@ extern "C" int rmt_n2_steady_sens(rmt_n2_handle* h, const void* y, int n_params,
                     "RMT_SENS_NP beside RMT_WITH_MARCH)");
     if (h->fp32) return fail("rmt_n2_steady_sens: fp64 only");
     if (n_params < 1 || n_params > RMT_N2_SENS_MAX) return fail("rmt_n2_steady_sens: 1..8 parameters (got %d)", n_params);
-    struct { int kind[RMT_N2_SENS_MAX], index[RMT_N2_SENS_MAX]; } desc;
-    std::memset(&desc, 0, sizeof(desc));
-    for (int p = 0; p < n_params; ++p) {
-        const int k = kinds[p], i = indices[p];
-        if (k < 0 || k > 4 || i < 0 || (k == 3 && i >= h->S) || (k == 4 && i >= h->NU) || (k < 3 && i != 0))
-            return fail("rmt_n2_steady_sens: parameter %d: kind %d (0 TM, 1 THETA_IN, 2 P0, 3 CIN[index], 4 user column "
-                        "[index]) with index %d is out of range (S = %d, NU = %d)", p, k, i, h->S, h->NU);
-        desc.kind[p] = k;
-        desc.index[p] = i;
-    }
-    PROFILE_READY(h);
+    ParamDesc desc;
+    if (build_desc(h, "rmt_n2_steady_sens", "parameter", 4, n_params, kinds, indices, &desc)) return 1;
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
     int N = h->N, E = h->E;
-    void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&n_params, (void*)&desc, (void*)&out,
-                    (void*)&h->d_flags};
+    void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&n_params, (void*)&desc, (void*)&out,
+                    (void*)&h->flags.p};
     return launch_lanes(h, h->f_sens, args);
 }
 
 // solver-config "frequency-response" (kernels/74_frequency.inc): the shifted tangent march over the converged state, one
 // (member, frequency) pair per lane.  Frequencies and peak nodes are HOST arrays, the result comes back to the HOST: the
-// call uploads, launches once, copies back and synchronises; its device buffers live for the call.
+// call uploads, launches once, copies back and synchronises; its device buffer lives for the call.
 #define RMT_N2_FREQ_MAX_INPUTS 4
 #define RMT_N2_FREQ_MAX_FREQUENCIES 4096
 extern "C" int rmt_n2_steady_freq(rmt_n2_handle* h, const void* y, int n_inputs, const int* kinds, const int* indices,
@@ -839,58 +842,36 @@ extern "C" int rmt_n2_steady_freq(rmt_n2_handle* h, const void* y, int n_inputs,
         return fail("rmt_n2_steady_freq: 1..%d inputs (got %d)", RMT_N2_FREQ_MAX_INPUTS, n_inputs);
     if (n_freq < 1 || n_freq > RMT_N2_FREQ_MAX_FREQUENCIES)
         return fail("rmt_n2_steady_freq: 1..%d frequencies (got %d)", RMT_N2_FREQ_MAX_FREQUENCIES, n_freq);
-    struct { int kind[RMT_N2_SENS_MAX], index[RMT_N2_SENS_MAX]; } desc;
-    std::memset(&desc, 0, sizeof(desc));
-    for (int p = 0; p < n_inputs; ++p) {
-        const int k = kinds[p], i = indices[p];
-        if (k < 0 || k > 3 || i < 0 || (k == 3 && i >= h->S) || (k < 3 && i != 0))
-            return fail("rmt_n2_steady_freq: input %d: kind %d (0 TM, 1 THETA_IN, 2 P0, 3 CIN[index]) with index %d is out of "
-                        "range (S = %d)", p, k, i, h->S);
-        desc.kind[p] = k;
-        desc.index[p] = i;
-    }
+    ParamDesc desc;
+    if (build_desc(h, "rmt_n2_steady_freq", "input", 3, n_inputs, kinds, indices, &desc)) return 1;
     for (int f = 0; f < n_freq; ++f)
         if (!(omegas_host[f] >= 0.0) || !std::isfinite(omegas_host[f]))
             return fail("rmt_n2_steady_freq: frequency %d is %g (finite and >= 0)", f, omegas_host[f]);
-    PROFILE_READY(h);
+    if (profile_missing(h)) return 1;
     ON_DEVICE(h);
     const size_t lanes = (size_t)h->E * (size_t)n_freq, rows = (size_t)n_inputs * (size_t)(h->V + 1) * 2;
     const size_t n_out = lanes * rows * 2, n_tab = profile ? lanes * rows * (size_t)h->N : 0, n_all = n_out + n_tab + lanes;
-    const size_t bytes = n_all * sizeof(double) + (size_t)n_freq * sizeof(double) + (size_t)h->E * sizeof(int);
+    const size_t omega_bytes = (size_t)n_freq * sizeof(double), peak_bytes = (size_t)h->E * sizeof(int);
     if ((lanes + 63) / 64 > 0x7fffffffULL) return fail("rmt_n2_steady_freq: %zu lanes are more than one grid holds", lanes);
-    char* buf = nullptr;
-    HIP_OK(hipMalloc((void**)&buf, bytes));
-    double* d_out = (double*)buf;
+    DevBuf buf;                                                   // (freed on every way out)
+    if (buf.reserve(h->stream, n_all * sizeof(double) + omega_bytes + peak_bytes)) return 1;
+    double* d_out = buf.as<double>();
     double* d_tab = profile ? d_out + n_out : nullptr;
     double* d_failed = d_out + n_out + n_tab;
     double* d_omegas = d_out + n_all;
     int* d_peak = (int*)(d_omegas + n_freq);
-    int rc = 0;
-#define FREQ_OK(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess && !rc) rc = fail("%s failed: %s", #call, hipGetErrorString(e_));     \
-    } while (0)
-    FREQ_OK(hipMemsetAsync(d_out, 0, n_all * sizeof(double), h->stream));
-    if (!rc) FREQ_OK(hipMemcpyAsync(d_omegas, omegas_host, (size_t)n_freq * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (!rc) FREQ_OK(hipMemcpyAsync(d_peak, peak_nodes_host, (size_t)h->E * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    if (!rc) FREQ_OK(hipStreamSynchronize(h->stream));            // (the host arrays are pageable: the copies have left them)
-    if (!rc) {
-        int N = h->N, E = h->E;
-        void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&n_freq, (void*)&n_inputs, (void*)&desc,
-                        (void*)&d_omegas, (void*)&d_peak, (void*)&profile, (void*)&d_out, (void*)&d_tab, (void*)&d_failed,
-                        (void*)&h->d_flags};
-        FREQ_OK(hipEventRecord(h->ev0, h->stream));
-        if (!rc) FREQ_OK(hipModuleLaunchKernel(h->f_freq, (unsigned)((lanes + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args,
-                                               nullptr));
-        if (!rc) FREQ_OK(hipEventRecord(h->ev1, h->stream));
-        if (!rc) h->timed = true;
-    }
-    if (!rc) FREQ_OK(hipMemcpyAsync(out_host, d_out, n_all * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FREQ_OK(hipStreamSynchronize(h->stream));
-    FREQ_OK(hipFree(buf));
-#undef FREQ_OK
-    return rc;
+    HIP_OK(hipMemsetAsync(d_out, 0, n_all * sizeof(double), h->stream));
+    HIP_OK(hipMemcpyAsync(d_omegas, omegas_host, omega_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(d_peak, peak_nodes_host, peak_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));                      // (the host arrays are pageable: the copies have left them)
+    int N = h->N, E = h->E;
+    void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&n_freq, (void*)&n_inputs, (void*)&desc,
+                    (void*)&d_omegas, (void*)&d_peak, (void*)&profile, (void*)&d_out, (void*)&d_tab, (void*)&d_failed,
+                    (void*)&h->flags.p};
+    if (launch_lanes(h, h->f_freq, args, lanes)) return 1;
+    HIP_OK(hipMemcpyAsync(out_host, d_out, n_all * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- campaign
@@ -902,8 +883,8 @@ static int campaign_ready(const rmt_n2_handle* h, const char* who, bool need_law
     if (!h->f_campaign)
         return fail("%s: this handle's code object has no rmt_n2_campaign_step (generate it with RMT_CAMPAIGN, "
                     "RMT_WITH_MARCH and RMT_PROFILE)", who);
-    if (!h->profiled || !h->d_profile) return fail("%s: no profile table has been set (rmt_n2_set_profile comes first)", who);
-    if (need_law && !h->d_law) return fail("%s: no deactivation law has been set (rmt_n2_set_campaign_law comes first)", who);
+    if (!h->profiled || !h->profile.p) return fail("%s: no profile table has been set (rmt_n2_set_profile comes first)", who);
+    if (need_law && !h->law.p) return fail("%s: no deactivation law has been set (rmt_n2_set_campaign_law comes first)", who);
     return 0;
 }
 
@@ -918,17 +899,7 @@ extern "C" int rmt_n2_set_campaign_law(rmt_n2_handle* h, const double* law_host)
                         "finite", e);
     }
     ON_DEVICE(h);
-    const size_t bytes = (size_t)h->E * RMT_N2_CAMPAIGN_LAW * sizeof(double);
-    HIP_OK(hipStreamSynchronize(h->stream));          // (a step in flight may still read the old rows)
-    double* buf = h->d_law;
-    if (!buf) HIP_OK(hipMalloc((void**)&buf, bytes));
-    const hipError_t e = hipMemcpy(buf, law_host, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (!h->d_law) (void)hipFree(buf);
-        return fail("rmt_n2_set_campaign_law: %s", hipGetErrorString(e));
-    }
-    h->d_law = buf;
-    return 0;
+    return upload_table(h, &h->law, "rmt_n2_set_campaign_law", {{law_host, (size_t)h->E * RMT_N2_CAMPAIGN_LAW * sizeof(double)}});
 }
 
 extern "C" int rmt_n2_campaign_step(rmt_n2_handle* h, void* y, double dt, double tol, int64_t max_iter, double* log_row,
@@ -941,8 +912,8 @@ extern "C" int rmt_n2_campaign_step(rmt_n2_handle* h, void* y, double dt, double
     ON_DEVICE(h);
     int N = h->N, E = h->E;
     long long mi = (long long)max_iter;
-    void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
-                    (void*)&h->d_flags, (void*)&h->d_profile, (void*)&h->d_law, (void*)&dt, (void*)&log_row};
+    void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
+                    (void*)&h->flags.p, (void*)&h->profile.p, (void*)&h->law.p, (void*)&dt, (void*)&log_row};
     return launch_lanes(h, h->f_campaign, args);
 }
 
@@ -950,8 +921,7 @@ extern "C" int rmt_n2_get_profile(rmt_n2_handle* h, double* table_host) {
     if (!h || !table_host) return fail("rmt_n2_get_profile: null argument");
     if (campaign_ready(h, "rmt_n2_get_profile", true)) return 1;
     ON_DEVICE(h);
-    HIP_OK(hipMemcpyAsync(table_host, h->d_profile, (size_t)h->E * 2 * (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
+    HIP_OK(hipMemcpyAsync(table_host, h->profile.p, profile_bytes(h), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -965,10 +935,12 @@ static int policy_ready(const rmt_n2_handle* h, const char* who, bool need_polic
         return fail("%s: this handle's code object has no rmt_n2_campaign_policy_step (generate it with RMT_CAMPAIGN_POLICY "
                     "beside RMT_CAMPAIGN, RMT_WITH_MARCH and RMT_PROFILE)", who);
     if (campaign_ready(h, who, true)) return 1;
-    if (need_policy && !h->d_policy)
+    if (need_policy && !h->policy.p)
         return fail("%s: no policy has been set (rmt_n2_set_campaign_policy comes first)", who);
     return 0;
 }
+// the carried coolant levels [E] behind the policy rows [E][RMT_N2_POLICY_ROW]
+static double* policy_levels(const rmt_n2_handle* h) { return h->policy.as<double>() + (size_t)h->E * RMT_N2_POLICY_ROW; }
 
 extern "C" int rmt_n2_set_campaign_policy(rmt_n2_handle* h, const double* rows_host, int component,
                                           const double* levels_host) {
@@ -985,17 +957,9 @@ extern "C" int rmt_n2_set_campaign_policy(rmt_n2_handle* h, const double* rows_h
                         "0, lo <= level <= hi, all finite)", e);
     }
     ON_DEVICE(h);
-    const size_t nrow = (size_t)h->E * RMT_N2_POLICY_ROW, bytes = (nrow + (size_t)h->E) * sizeof(double);
-    HIP_OK(hipStreamSynchronize(h->stream));          // (a step in flight may still read the old rows)
-    double* buf = h->d_policy;
-    if (!buf) HIP_OK(hipMalloc((void**)&buf, bytes));
-    hipError_t e = hipMemcpy(buf, rows_host, nrow * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(buf + nrow, levels_host, (size_t)h->E * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (!h->d_policy) (void)hipFree(buf);
-        return fail("rmt_n2_set_campaign_policy: %s", hipGetErrorString(e));
-    }
-    h->d_policy = buf;
+    if (upload_table(h, &h->policy, "rmt_n2_set_campaign_policy",
+                     {{rows_host, (size_t)h->E * RMT_N2_POLICY_ROW * sizeof(double)}, {levels_host, (size_t)h->E * sizeof(double)}}))
+        return 1;
     h->policy_comp = component;
     return 0;
 }
@@ -1011,10 +975,10 @@ extern "C" int rmt_n2_campaign_policy_step(rmt_n2_handle* h, void* y, double dt,
     ON_DEVICE(h);
     int N = h->N, E = h->E, comp = h->policy_comp;
     long long mi = (long long)max_iter;
-    double* levels = h->d_policy + (size_t)E * RMT_N2_POLICY_ROW;
-    void* args[] = {(void*)&y, (void*)&h->d_members, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
-                    (void*)&h->d_flags, (void*)&h->d_profile, (void*)&h->d_law, (void*)&dt, (void*)&log_row,
-                    (void*)&h->d_policy, (void*)&levels, (void*)&policy_row, (void*)&comp, (void*)&max_evaluations};
+    double* levels = policy_levels(h);
+    void* args[] = {(void*)&y, (void*)&h->members.p, (void*)&N, (void*)&E, (void*)&tol, (void*)&mi, (void*)&stats,
+                    (void*)&h->flags.p, (void*)&h->profile.p, (void*)&h->law.p, (void*)&dt, (void*)&log_row,
+                    (void*)&h->policy.p, (void*)&levels, (void*)&policy_row, (void*)&comp, (void*)&max_evaluations};
     return launch_lanes(h, h->f_policy, args);
 }
 
@@ -1022,8 +986,7 @@ extern "C" int rmt_n2_get_campaign_level(rmt_n2_handle* h, double* levels_host) 
     if (!h || !levels_host) return fail("rmt_n2_get_campaign_level: null argument");
     if (policy_ready(h, "rmt_n2_get_campaign_level", true)) return 1;
     ON_DEVICE(h);
-    HIP_OK(hipMemcpyAsync(levels_host, h->d_policy + (size_t)h->E * RMT_N2_POLICY_ROW, (size_t)h->E * sizeof(double),
-                          hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemcpyAsync(levels_host, policy_levels(h), (size_t)h->E * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -1032,7 +995,7 @@ extern "C" int rmt_n2_fallbacks(rmt_n2_handle* h, uint64_t* count) {
     if (!h || !count) return fail("null argument");
     ON_DEVICE(h);
     unsigned c = 0;
-    HIP_OK(hipMemcpyAsync(&c, h->d_flags + h->E, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemcpyAsync(&c, h->status_words() + h->E, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     *count = c;
     return 0;
@@ -1041,11 +1004,51 @@ extern "C" int rmt_n2_fallbacks(rmt_n2_handle* h, uint64_t* count) {
 extern "C" int rmt_n2_status(rmt_n2_handle* h, uint32_t* flags_host) {
     if (!h || !flags_host) return fail("null argument");
     ON_DEVICE(h);
-    HIP_OK(hipMemcpyAsync(flags_host, h->d_flags, (size_t)h->E * sizeof(unsigned), hipMemcpyDeviceToHost,
+    HIP_OK(hipMemcpyAsync(flags_host, h->flags.p, (size_t)h->E * sizeof(unsigned), hipMemcpyDeviceToHost,
                           h->stream));
-    HIP_OK(hipMemsetAsync(h->d_flags, 0, (size_t)h->E * sizeof(unsigned), h->stream));
+    HIP_OK(hipMemsetAsync(h->flags.p, 0, (size_t)h->E * sizeof(unsigned), h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- side modules
+// What the monitor, the controller and the fit share: a mechanism-independent module loaded on the device that was current
+// at creation, one create and one destroy.
+struct SideModule {
+    int device = 0;
+    hipModule_t module = nullptr;
+    ~SideModule() {                          // (on the module's device: side_destroy switches to it, side_create has not left it)
+        if (module) (void)hipModuleUnload(module);
+    }
+};
+template <class M>
+struct SideKernel { const char* name; hipFunction_t M::*f; };
+
+// ``who``: the entry point, ``what``: "monitor" / "controller" / "fit", for the error texts; a module that lacks one of its
+// kernels is unloaded again
+template <class M>
+static int side_create(const char* who, const char* what, const void* code, size_t size, M** out,
+                       std::initializer_list<SideKernel<M>> kernels) {
+    if (!code || !size || !out) return fail("%s: null argument", who);
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail("no HIP device available: the %s has no CPU fallback", what);
+    std::unique_ptr<M> m(new M());
+    hipError_t e = hipGetDevice(&m->device);
+    if (e == hipSuccess) e = hipModuleLoadData(&m->module, code);
+    for (const SideKernel<M>& k : kernels)
+        if (e == hipSuccess) e = hipModuleGetFunction(&(m.get()->*k.f), m->module, k.name);
+    if (e != hipSuccess) return fail("%s: %s", who, hipGetErrorString(e));
+    *out = m.release();
+    return 0;
+}
+
+template <class M>
+static void side_destroy(M* m) {
+    if (!m) return;
+    DeviceGuard guard_(m->device);
+    delete m;
 }
 
 // ---------------------------------------------------------------------------------------------- monitor
@@ -1064,62 +1067,22 @@ extern "C" int rmt_n2_status(rmt_n2_handle* h, uint32_t* flags_host) {
 #define RMT_N2_MONITOR_WAVE_BYTES 8192
 #define RMT_N2_MONITOR_ROWS_PER_CU 4
 
-// What the monitor and the controller share: a module loaded on the device that was current at creation
-struct SideModule { int device = 0; hipModule_t module = nullptr; };
-struct SideKernel { const char* name; hipFunction_t* f; };
-
-static void side_unload(SideModule* m) {
-    DeviceGuard guard_(m->device);
-    if (m->module) (void)hipModuleUnload(m->module);
-}
-
-// the loader of both (``who``: the entry point, ``what``: "monitor" / "controller", for the error texts); a module that
-// lacks one of its kernels is unloaded again
-static int side_load(SideModule* m, const char* who, const char* what, const void* code,
-                     std::initializer_list<SideKernel> kernels) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail("no HIP device available: the %s has no CPU fallback", what);
-    hipError_t e = hipGetDevice(&m->device);
-    if (e == hipSuccess) e = hipModuleLoadData(&m->module, code);
-    for (const SideKernel& k : kernels)
-        if (e == hipSuccess) e = hipModuleGetFunction(k.f, m->module, k.name);
-    if (e == hipSuccess) return 0;
-    fail("%s: %s", who, hipGetErrorString(e));
-    side_unload(m);
-    return 1;
-}
-
 struct rmt_n2_monitor : SideModule {
     int n_cus = 0, last_rows_per_block = 0;
     hipFunction_t f64 = nullptr, f32 = nullptr;
 };
 
 extern "C" const char* rmt_n2_monitor_source(void) { return k_monitor_source; }
-
-extern "C" void rmt_n2_monitor_destroy(rmt_n2_monitor* m) {
-    if (!m) return;
-    side_unload(m);
-    delete m;
-}
-
+extern "C" void rmt_n2_monitor_destroy(rmt_n2_monitor* m) { side_destroy(m); }
 extern "C" int rmt_n2_monitor_create(const void* code, size_t size, rmt_n2_monitor** out) {
-    if (!code || !size || !out) return fail("rmt_n2_monitor_create: null argument");
+    if (side_create("rmt_n2_monitor_create", "monitor", code, size, out,
+                    {{"rmt_n2_monitor_rows_f64", &rmt_n2_monitor::f64}, {"rmt_n2_monitor_rows_f32", &rmt_n2_monitor::f32}}))
+        return 1;
+    const hipError_t e = hipDeviceGetAttribute(&(*out)->n_cus, hipDeviceAttributeMultiprocessorCount, (*out)->device);
+    if (e == hipSuccess) return 0;
+    side_destroy(*out);
     *out = nullptr;
-    rmt_n2_monitor* m = new rmt_n2_monitor();
-    if (side_load(m, "rmt_n2_monitor_create", "monitor", code,
-                  {{"rmt_n2_monitor_rows_f64", &m->f64}, {"rmt_n2_monitor_rows_f32", &m->f32}})) {
-        delete m;
-        return 1;
-    }
-    const hipError_t e = hipDeviceGetAttribute(&m->n_cus, hipDeviceAttributeMultiprocessorCount, m->device);
-    if (e != hipSuccess) {
-        fail("rmt_n2_monitor_create: %s", hipGetErrorString(e));
-        rmt_n2_monitor_destroy(m);
-        return 1;
-    }
-    *out = m;
-    return 0;
+    return fail("rmt_n2_monitor_create: %s", hipGetErrorString(e));
 }
 
 extern "C" int rmt_n2_monitor_reduce(rmt_n2_monitor* m, void* hip_stream, const void* y, const void* dydt_or_null,
@@ -1152,8 +1115,7 @@ extern "C" int rmt_n2_monitor_reduce(rmt_n2_monitor* m, void* hip_stream, const 
     const long long cap = (long long)m->n_cus * RMT_N2_MONITOR_WGS_PER_CU;
     if (grid > cap) grid = cap;
     void* args[] = {(void*)&y, (void*)&dydt_or_null, (void*)&out, (void*)&rows, (void*)&N, (void*)&rows_per_block};
-    HIP_OK(hipModuleLaunchKernel(fp32 ? m->f32 : m->f64, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, 0,
-                                 (hipStream_t)hip_stream, args, nullptr));
+    if (launch((hipStream_t)hip_stream, fp32 ? m->f32 : m->f64, (size_t)grid, block, args)) return 1;
     m->last_rows_per_block = rows_per_block;
     return 0;
 }
@@ -1172,23 +1134,10 @@ struct rmt_n2_control : SideModule {
 };
 
 extern "C" const char* rmt_n2_control_source(void) { return k_control_source; }
-
-extern "C" void rmt_n2_control_destroy(rmt_n2_control* c) {
-    if (!c) return;
-    side_unload(c);
-    delete c;
-}
-
+extern "C" void rmt_n2_control_destroy(rmt_n2_control* c) { side_destroy(c); }
 extern "C" int rmt_n2_control_create(const void* code, size_t size, rmt_n2_control** out) {
-    if (!code || !size || !out) return fail("rmt_n2_control_create: null argument");
-    *out = nullptr;
-    rmt_n2_control* c = new rmt_n2_control();
-    if (side_load(c, "rmt_n2_control_create", "controller", code, {{"rmt_n2_control_update_f64", &c->f_update}})) {
-        delete c;
-        return 1;
-    }
-    *out = c;
-    return 0;
+    return side_create("rmt_n2_control_create", "controller", code, size, out,
+                       {{"rmt_n2_control_update_f64", &rmt_n2_control::f_update}});
 }
 
 extern "C" int rmt_n2_control_update(rmt_n2_control* c, rmt_n2_handle* h, const double* y, int V, int N,
@@ -1212,12 +1161,10 @@ extern "C" int rmt_n2_control_update(rmt_n2_control* c, rmt_n2_handle* h, const 
     const int waves = RMT_N2_CONTROL_BLOCK / 64;
     int grid = (E + waves - 1) / waves;
     if (grid > RMT_N2_CONTROL_MAX_GRID) grid = RMT_N2_CONTROL_MAX_GRID;
-    void* args[] = {(void*)&y,   (void*)&h->d_members, (void*)&params, (void*)&setpoint, (void*)&state,
+    void* args[] = {(void*)&y,   (void*)&h->members.p, (void*)&params, (void*)&setpoint, (void*)&state,
                     (void*)&log, (void*)&E,            (void*)&S,      (void*)&V,        (void*)&N,
                     (void*)&width, (void*)&tail_at,    (void*)&field,  (void*)&hold};
-    HIP_OK(hipModuleLaunchKernel(c->f_update, (unsigned)grid, 1, 1, RMT_N2_CONTROL_BLOCK, 1, 1, 0, h->stream, args,
-                                 nullptr));
-    return 0;
+    return launch(h->stream, c->f_update, grid, RMT_N2_CONTROL_BLOCK, args);
 }
 
 // ---------------------------------------------------------------------------------------------- fit
@@ -1234,24 +1181,10 @@ struct rmt_n2_fit : SideModule {
 };
 
 extern "C" const char* rmt_n2_fit_source(void) { return k_fit_source; }
-
-extern "C" void rmt_n2_fit_destroy(rmt_n2_fit* f) {
-    if (!f) return;
-    side_unload(f);
-    delete f;
-}
-
+extern "C" void rmt_n2_fit_destroy(rmt_n2_fit* f) { side_destroy(f); }
 extern "C" int rmt_n2_fit_create(const void* code, size_t size, rmt_n2_fit** out) {
-    if (!code || !size || !out) return fail("rmt_n2_fit_create: null argument");
-    *out = nullptr;
-    rmt_n2_fit* f = new rmt_n2_fit();
-    if (side_load(f, "rmt_n2_fit_create", "fit", code,
-                  {{"rmt_n2_fit_residuals_f64", &f->f_residuals}, {"rmt_n2_fit_update_f64", &f->f_update}})) {
-        delete f;
-        return 1;
-    }
-    *out = f;
-    return 0;
+    return side_create("rmt_n2_fit_create", "fit", code, size, out,
+                       {{"rmt_n2_fit_residuals_f64", &rmt_n2_fit::f_residuals}, {"rmt_n2_fit_update_f64", &rmt_n2_fit::f_update}});
 }
 
 extern "C" int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens,
@@ -1288,14 +1221,12 @@ extern "C" int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y,
     const int waves = RMT_N2_FIT_BLOCK / 64;
     int grid = (E + waves - 1) / waves;
     if (grid > RMT_N2_FIT_MAX_GRID) grid = RMT_N2_FIT_MAX_GRID;
-    void* args1[] = {(void*)&y,    (void*)&sens,    (void*)&stats, (void*)&h->d_members, (void*)&meas,
+    void* args1[] = {(void*)&y,    (void*)&sens,    (void*)&stats, (void*)&h->members.p, (void*)&meas,
                      (void*)&pred, (void*)&contrib, (void*)&E,     (void*)&S,            (void*)&V,
                      (void*)&N,    (void*)&n_params, (void*)&MQ,   (void*)&width};
-    HIP_OK(hipModuleLaunchKernel(f->f_residuals, (unsigned)grid, 1, 1, RMT_N2_FIT_BLOCK, 1, 1, 0, h->stream, args1,
-                                 nullptr));
-    void* args2[] = {(void*)&contrib, (void*)&h->d_members, (void*)&state,    (void*)&log_slice, (void*)&E,
+    if (launch(h->stream, f->f_residuals, grid, RMT_N2_FIT_BLOCK, args1)) return 1;
+    void* args2[] = {(void*)&contrib, (void*)&h->members.p, (void*)&state,    (void*)&log_slice, (void*)&E,
                      (void*)&S,       (void*)&n_params,     (void*)&width,    (void*)&cols,      (void*)&tolerance,
                      (void*)&damping0};
-    HIP_OK(hipModuleLaunchKernel(f->f_update, 1, 1, 1, 64, 1, 1, 0, h->stream, args2, nullptr));
-    return 0;
+    return launch(h->stream, f->f_update, 1, 64, args2);
 }

@@ -391,6 +391,29 @@ void rmt_n2_fit_destroy(rmt_n2_fit* f);
 int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens, const rmt_n2_stats* stats, int S,
                     int V, int N, int n_params, const int* columns, const double* meas, int MQ, double* contrib,
                     double* pred, double* state, double* log_slice, double tolerance, double damping0);
+/* rmt_n2_fit_step with log-scaled and bounded parameters and measurements along the bed: the sibling kernels
+ * rmt_n2_fit_residuals_ex_f64 and rmt_n2_fit_update_ex_f64 of the same translation unit (rmt_n2_fit_create loads all four).
+ * Every argument of rmt_n2_fit_step with the same meaning and the same checks, except
+ *   meas      two more codes: S+2 the temperature (K), S+3+i the mole fraction of species i, at the entry's position
+ *   log_slice DEVICE [70] doubles: the 68 of rmt_n2_fit_step, then the parameters of the current point that sit on their
+ *             lower / on their upper bound with the gradient pushing outwards, one bit each (also state words 76, 77)
+ * and three more:
+ *   pos       DEVICE [E][MQ][2] doubles {n0, f} per entry of meas (read for the two new codes only): the prediction is
+ *             (1-f) q(n0) + f q(n0+1) with q the node temperature or the node mole fraction of the clamped node state, the
+ *             Jacobian row the same combination; 0 <= n0 <= N-2 (a record outside fails the experiment)
+ *   log_scale HOST n_params ints: 1 = the law works in theta = ln p for this parameter (J's column is multiplied by the
+ *             member's own value of the constant), 0 = in p
+ *   box       HOST [4][8] doubles {lo in p, hi in p, lo in theta, hi in theta}, -HUGE_VAL / HUGE_VAL where open; lo < hi
+ * The law, in order: the active set A = {j: p_j <= lo_j and g_j > 0, or p_j >= hi_j and g_j < 0} - rows and columns of
+ * H + lambda D become the unit vector, g_j = 0, and all parameters in A is converged -; the step, with theta + delta clamped
+ * into the box; the predicted reduction - without a clamped component that of rmt_n2_fit_step, else the model's own
+ * -(g^T d + 1/2 d^T H d), which must be > 0 or lambda grows as after a failed pivot -; converged when max |d_j| / s_j <=
+ * tolerance, s_j = 1 for a log parameter; the trial p + d, p exp(d) for a log parameter, the bound itself where the step was
+ * clamped, kept inside the box in p.  Without flags, bounds and new codes it computes what rmt_n2_fit_step computes. */
+int rmt_n2_fit_step_ex(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens, const rmt_n2_stats* stats,
+                       int S, int V, int N, int n_params, const int* columns, const double* meas, int MQ, double* contrib,
+                       double* pred, double* state, double* log_slice, double tolerance, double damping0,
+                       const double* pos, const int* log_scale, const double* box);
 
 const char* rmt_n2_last_error(void);
 int rmt_n2_abi_version(void);

@@ -1177,45 +1177,65 @@ extern "C" int rmt_n2_control_update(rmt_n2_control* c, rmt_n2_handle* h, const 
 #define RMT_N2_FIT_MAX_QUANTITIES 64
 
 struct rmt_n2_fit : SideModule {
-    hipFunction_t f_residuals = nullptr, f_update = nullptr;
+    hipFunction_t f_residuals = nullptr, f_update = nullptr, f_residuals_ex = nullptr, f_update_ex = nullptr;
 };
 
 extern "C" const char* rmt_n2_fit_source(void) { return k_fit_source; }
 extern "C" void rmt_n2_fit_destroy(rmt_n2_fit* f) { side_destroy(f); }
 extern "C" int rmt_n2_fit_create(const void* code, size_t size, rmt_n2_fit** out) {
     return side_create("rmt_n2_fit_create", "fit", code, size, out,
-                       {{"rmt_n2_fit_residuals_f64", &rmt_n2_fit::f_residuals}, {"rmt_n2_fit_update_f64", &rmt_n2_fit::f_update}});
+                       {{"rmt_n2_fit_residuals_f64", &rmt_n2_fit::f_residuals},
+                        {"rmt_n2_fit_update_f64", &rmt_n2_fit::f_update},
+                        {"rmt_n2_fit_residuals_ex_f64", &rmt_n2_fit::f_residuals_ex},
+                        {"rmt_n2_fit_update_ex_f64", &rmt_n2_fit::f_update_ex}});
 }
 
-extern "C" int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens,
-                               const rmt_n2_stats* stats, int S, int V, int N, int n_params, const int* columns,
-                               const double* meas, int MQ, double* contrib, double* pred, double* state, double* log_slice,
-                               double tolerance, double damping0) {
+// rmt_n2_fit_step and rmt_n2_fit_step_ex: the same checks and the same two launches; ``who`` names the entry point in the
+// error texts.  pos == nullptr: the plain pair of kernels.
+static int fit_step(const char* who, rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens,
+                    const rmt_n2_stats* stats, int S, int V, int N, int n_params, const int* columns, const double* meas,
+                    int MQ, double* contrib, double* pred, double* state, double* log_slice, double tolerance,
+                    double damping0, const double* pos, const int* log_scale, const double* box) {
+    const bool ex = pos != nullptr;
     if (!f || !h || !y || !sens || !stats || !columns || !meas || !contrib || !pred || !state || !log_slice)
-        return fail("rmt_n2_fit_step: null argument");
-    if (n_params < 1 || n_params > RMT_N2_FIT_MAX_PARAMS)
-        return fail("rmt_n2_fit_step: 1..8 parameters (got %d)", n_params);
+        return fail("%s: null argument", who);
+    if (n_params < 1 || n_params > RMT_N2_FIT_MAX_PARAMS) return fail("%s: 1..8 parameters (got %d)", who, n_params);
     if (!h->f_sens || !h->f_march)
-        return fail("rmt_n2_fit_step: this handle's code object is not the sensitivity unit (no rmt_n2_steady_sens beside "
-                    "rmt_n2_steady_march)");
-    if (h->fp32) return fail("rmt_n2_fit_step: fp64 handles only");
+        return fail("%s: this handle's code object is not the sensitivity unit (no rmt_n2_steady_sens beside "
+                    "rmt_n2_steady_march)", who);
+    if (h->fp32) return fail("%s: fp64 handles only", who);
     if (h->device != f->device)
-        return fail("rmt_n2_fit_step: the handle lives on device %d, the fit on %d", h->device, f->device);
+        return fail("%s: the handle lives on device %d, the fit on %d", who, h->device, f->device);
     if (S != h->S || V != h->V || N != h->N)
-        return fail("rmt_n2_fit_step: S=%d V=%d N=%d are not the handle's (%d, %d, %d)", S, V, N, h->S, h->V, h->N);
+        return fail("%s: S=%d V=%d N=%d are not the handle's (%d, %d, %d)", who, S, V, N, h->S, h->V, h->N);
     if (MQ < 1 || MQ > RMT_N2_FIT_MAX_QUANTITIES)
-        return fail("rmt_n2_fit_step: 1..%d measured quantities per experiment (got %d)", RMT_N2_FIT_MAX_QUANTITIES, MQ);
-    if (!(tolerance >= 0) || !(damping0 > 0)) return fail("rmt_n2_fit_step: tolerance >= 0 and damping > 0");
+        return fail("%s: 1..%d measured quantities per experiment (got %d)", who, RMT_N2_FIT_MAX_QUANTITIES, MQ);
+    if (!(tolerance >= 0) || !(damping0 > 0)) return fail("%s: tolerance >= 0 and damping > 0", who);
     struct { int col[RMT_N2_FIT_MAX_PARAMS]; } cols;
+    struct { int col[RMT_N2_FIT_MAX_PARAMS]; int log[RMT_N2_FIT_MAX_PARAMS]; } scale;
+    struct { double v[4][RMT_N2_FIT_MAX_PARAMS]; int log[RMT_N2_FIT_MAX_PARAMS]; } bx;
     std::memset(&cols, 0, sizeof(cols));
+    std::memset(&scale, 0, sizeof(scale));
+    std::memset(&bx, 0, sizeof(bx));
     for (int j = 0; j < n_params; ++j) {
         if (columns[j] < 0 || columns[j] >= h->NU)
-            return fail("rmt_n2_fit_step: parameter %d: user column %d is out of range (NU = %d)", j, columns[j], h->NU);
-        cols.col[j] = columns[j];
+            return fail("%s: parameter %d: user column %d is out of range (NU = %d)", who, j, columns[j], h->NU);
+        cols.col[j] = scale.col[j] = columns[j];
+    }
+    if (ex) {
+        if (N < 2) return fail("%s: positions along the bed need N >= 2 (got %d)", who, N);
+        for (int j = 0; j < RMT_N2_FIT_MAX_PARAMS; ++j) {
+            const bool in = j < n_params;
+            scale.log[j] = bx.log[j] = in && log_scale[j] ? 1 : 0;
+            for (int k = 0; k < 4; ++k)
+                bx.v[k][j] = in ? box[k * RMT_N2_FIT_MAX_PARAMS + j] : (k % 2 ? HUGE_VAL : -HUGE_VAL);
+            if (in && !(bx.v[0][j] < bx.v[1][j] && bx.v[2][j] < bx.v[3][j]))
+                return fail("%s: parameter %d: the bounds must be lo < hi in p and in theta", who, j);
+        }
     }
     if (((size_t)y | (size_t)sens | (size_t)stats | (size_t)meas | (size_t)contrib | (size_t)pred | (size_t)state |
-         (size_t)log_slice) % sizeof(double))
-        return fail("rmt_n2_fit_step: misaligned pointer");
+         (size_t)log_slice | (size_t)pos) % sizeof(double))
+        return fail("%s: misaligned pointer", who);
     ON_DEVICE(h);
     int E = h->E, width = RMT_N2_MEMBER_FIXED + h->S + h->NU;
     const int waves = RMT_N2_FIT_BLOCK / 64;
@@ -1223,10 +1243,29 @@ extern "C" int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y,
     if (grid > RMT_N2_FIT_MAX_GRID) grid = RMT_N2_FIT_MAX_GRID;
     void* args1[] = {(void*)&y,    (void*)&sens,    (void*)&stats, (void*)&h->members.p, (void*)&meas,
                      (void*)&pred, (void*)&contrib, (void*)&E,     (void*)&S,            (void*)&V,
-                     (void*)&N,    (void*)&n_params, (void*)&MQ,   (void*)&width};
-    if (launch(h->stream, f->f_residuals, grid, RMT_N2_FIT_BLOCK, args1)) return 1;
+                     (void*)&N,    (void*)&n_params, (void*)&MQ,   (void*)&width,        (void*)&pos,
+                     (void*)&scale};                  // (the plain kernel takes the first 14)
+    if (launch(h->stream, ex ? f->f_residuals_ex : f->f_residuals, grid, RMT_N2_FIT_BLOCK, args1)) return 1;
     void* args2[] = {(void*)&contrib, (void*)&h->members.p, (void*)&state,    (void*)&log_slice, (void*)&E,
                      (void*)&S,       (void*)&n_params,     (void*)&width,    (void*)&cols,      (void*)&tolerance,
-                     (void*)&damping0};
-    return launch(h->stream, f->f_update, 1, 64, args2);
+                     (void*)&damping0, (void*)&bx};   // (the plain kernel takes the first 11)
+    return launch(h->stream, ex ? f->f_update_ex : f->f_update, 1, 64, args2);
+}
+
+extern "C" int rmt_n2_fit_step(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens,
+                               const rmt_n2_stats* stats, int S, int V, int N, int n_params, const int* columns,
+                               const double* meas, int MQ, double* contrib, double* pred, double* state, double* log_slice,
+                               double tolerance, double damping0) {
+    return fit_step("rmt_n2_fit_step", f, h, y, sens, stats, S, V, N, n_params, columns, meas, MQ, contrib, pred, state,
+                    log_slice, tolerance, damping0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rmt_n2_fit_step_ex(rmt_n2_fit* f, rmt_n2_handle* h, const double* y, const double* sens,
+                                  const rmt_n2_stats* stats, int S, int V, int N, int n_params, const int* columns,
+                                  const double* meas, int MQ, double* contrib, double* pred, double* state,
+                                  double* log_slice, double tolerance, double damping0, const double* pos,
+                                  const int* log_scale, const double* box) {
+    if (!pos || !log_scale || !box) return fail("rmt_n2_fit_step_ex: null argument");
+    return fit_step("rmt_n2_fit_step_ex", f, h, y, sens, stats, S, V, N, n_params, columns, meas, MQ, contrib, pred, state,
+                    log_slice, tolerance, damping0, pos, log_scale, box);
 }

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import campaign, frequency, hipbind, initial, monitor, plan, sensitivity
+from . import campaign, fit, frequency, hipbind, initial, monitor, plan, sensitivity
 from .codeplan import code_plan, compile_plan, device_arch, forced_tail, freq_plan, is_forced, is_profiled, march_plan, sens_plan
 from .lowering import FLAG_DIV0, FLAG_DOMAIN, FLAG_NONFINITE, FLAG_OVERFLOW, FLAG_STEP
 from .settings import DEVICE_DEFAULTS
@@ -385,11 +385,12 @@ class N2Device:
         """The status words of the handle steady_freq ran on, read and cleared (synchronises)."""
         return (self.freq if self.freq is not None else self).status()
 
-    def fit_step(self, y, sens, loop, k):
+    def fit_step(self, y, sens, loop, k, extended=False):
         """Queue pass ``k`` of a fit on the device's stream, behind steady_march and steady_sens on this handle
         (csrc/fit_kernels.inc): the residuals and their reduction over the members (the experiments) from the state y and
         the sensitivity buffer ``sens``, then the Levenberg-Marquardt step, which writes slice k of the loop's log and the
-        trial values into the fitted columns of this device's rows.  ``loop``: the run's FitLoop (n2.py).  Nothing is
+        trial values into the fitted columns of this device's rows.  ``loop``: the run's FitLoop (n2.py); ``extended``: the
+        loop carries the position table, the scale flags and the box, and the sibling kernels run (rmt_n2_fit_step_ex).  Nothing is
         copied or synchronised.  Needs the sensitivity unit (sens_plan) in fp64."""
         self._chk_state(y)
         if str(self.defines.get(sensitivity.DEFINE, "0")) != "1" or self.fp32:
@@ -397,9 +398,14 @@ class N2Device:
         P = len(loop.columns)
         assert loop.E == self.E and sens.is_cuda and sens.dtype == self.torch.float64 and sens.is_contiguous() \
             and sens.numel() == self.E*P*(self.mech.V + 1)*self.N, "sensitivity buffer must be [E][NP][V+1][N]"
-        loop.kernel.step(self.h, y.data_ptr(), sens.data_ptr(), self._stats.data_ptr(), self.mech.S, self.mech.V, self.N,
-                         loop.columns, loop.meas.data_ptr(), loop.MQ, loop.contrib.data_ptr(), loop.pred.data_ptr(),
-                         loop.state.data_ptr(), loop.log[k].data_ptr(), loop.tolerance, loop.damping)
+        args = (self.h, y.data_ptr(), sens.data_ptr(), self._stats.data_ptr(), self.mech.S, self.mech.V, self.N,
+                loop.columns, loop.meas.data_ptr(), loop.MQ, loop.contrib.data_ptr(), loop.pred.data_ptr(),
+                loop.state.data_ptr(), loop.log[k].data_ptr(), loop.tolerance, loop.damping)
+        if not extended:                                # a loop without the new data: the present call
+            loop.kernel.step(*args)
+        else:                                           # log-scaled or bounded parameters, data along the bed
+            assert loop.log.shape[1] == fit.LOG_EX and loop.pos.numel() == self.E*loop.MQ*2
+            loop.kernel.step_ex(*args, loop.pos.data_ptr(), loop.flags, loop.box)
 
     def sens_status(self):
         """The status words of the handle steady_sens ran on, read and cleared (synchronises)."""

@@ -104,6 +104,7 @@ def lib():
     L.rmt_n2_fit_destroy.restype = None
     L.rmt_n2_fit_step.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), vp, C.c_int,
                                   vp, vp, vp, vp, dbl, dbl]
+    L.rmt_n2_fit_step_ex.argtypes = L.rmt_n2_fit_step.argtypes + [vp, C.POINTER(C.c_int), C.POINTER(dbl)]
     L.rmt_n2_hiprtc_path.restype = cp
     L.rmt_n2_compile_options.restype = cp
     if L.rmt_n2_abi_version() != ABI_VERSION:
@@ -232,6 +233,20 @@ class Fit(_SideModule):
         check(lib().rmt_n2_fit_step(self.h, handle, ptr(y_ptr), ptr(sens_ptr), ptr(stats_ptr), int(S), int(V), int(N),
                                     len(columns), cols, ptr(meas_ptr), int(MQ), ptr(contrib_ptr), ptr(pred_ptr),
                                     ptr(state_ptr), ptr(log_ptr), float(tolerance), float(damping)))
+
+    def step_ex(self, handle, y_ptr, sens_ptr, stats_ptr, S, V, N, columns, meas_ptr, MQ, contrib_ptr, pred_ptr, state_ptr,
+                log_ptr, tolerance, damping, pos_ptr, flags, box):
+        """``step`` with the sibling kernels (rmt_n2_fit_step_ex): ``pos_ptr`` the position table on the device,
+        ``flags`` [P] 1 = log-scaled, ``box`` [4][8] doubles (fit.box); the log slice is 70 doubles wide."""
+        def ptr(p):
+            return C.c_void_p(p) if p else None
+        cols = (C.c_int*len(columns))(*[int(c) for c in columns])
+        scale = (C.c_int*len(columns))(*[int(bool(f)) for f in flags])
+        bx = (C.c_double*32)(*[float(v) for row in box for v in row])
+        check(lib().rmt_n2_fit_step_ex(self.h, handle, ptr(y_ptr), ptr(sens_ptr), ptr(stats_ptr), int(S), int(V), int(N),
+                                       len(columns), cols, ptr(meas_ptr), int(MQ), ptr(contrib_ptr), ptr(pred_ptr),
+                                       ptr(state_ptr), ptr(log_ptr), float(tolerance), float(damping), ptr(pos_ptr), scale,
+                                       bx))
 
 
 def compile_source(source, arch="gfx950", extra_opts=""):

@@ -684,19 +684,25 @@ def run_campaign(modelInput, members_inputs, cam, pack_all, result):
 class FitLoop:
     """The device side of one fit (fit.Fit): the kernels' module and their buffers - the measurement table [E][MQ][3], the
     experiments' contributions [E][46] and predictions [E][MQ], the LM state [80] and the log [passes][68], read once per
-    batch of iterations."""
+    batch of iterations.  A spec with log-scaled or bounded parameters or data along the bed (ft.extended) takes the
+    sibling kernels: the position table ``pos`` [E][MQ][2], the scale flags, the box, and a log 70 wide; any other spec
+    (``pos`` None) takes rmt_n2_fit_step as before."""
 
     def __init__(self, ft, dev, columns, passes):
         torch = dev.torch
         self.E, self.MQ, self.columns = ft.E, ft.MQ, list(columns)
         self.tolerance, self.damping = ft.tolerance, ft.damping
+        self.pos, width = None, fit.LOG
+        if ft.extended:
+            self.pos = torch.from_numpy(np.ascontiguousarray(ft.position_table(dev.N))).to(dev.device)
+            self.flags, self.box, width = list(ft.flags), ft.box(), fit.LOG_EX
         with torch.cuda.device(dev.device):
             self.kernel = hipbind.Fit(device_arch(dev.device))
         self.meas = torch.from_numpy(np.ascontiguousarray(ft.table())).to(dev.device)
         self.contrib = torch.zeros((ft.E, fit.CONTRIB), dtype=torch.float64, device=dev.device)
         self.pred = torch.zeros((ft.E, ft.MQ), dtype=torch.float64, device=dev.device)
         self.state = torch.zeros(fit.STATE, dtype=torch.float64, device=dev.device)
-        self.log = torch.zeros((passes, fit.LOG), dtype=torch.float64, device=dev.device)
+        self.log = torch.zeros((passes, width), dtype=torch.float64, device=dev.device)
 
     def close(self):
         self.kernel.close()
@@ -733,11 +739,12 @@ def run_fit(modelInput, ft, pack_all, result):
         def queue(k):
             dev.steady_march(y, tol, its)
             dev.steady_sens(y, kinds, indices, raw)
-            dev.fit_step(y, raw, loop, k)
+            dev.fit_step(y, raw, loop, k, extended=ft.extended)
 
         def describe(row):
-            return "cost %.12g at %s" % (row[1], ", ".join("%s = %.12g" % (nm, v) for nm, v in
-                                                           zip(ft.names, row[fit.LOG_PCUR:fit.LOG_PCUR + ft.NP])))
+            return "cost %.12g at %s%s" % (row[1], ", ".join("%s = %.12g" % (nm, v) for nm, v in
+                                                             zip(ft.names, row[fit.LOG_PCUR:fit.LOG_PCUR + ft.NP])),
+                                           ft.bounds_text(row))
         logs, n, done = [], 0, False
         while n < ft.max_iterations and not done:
             hi = min(ft.max_iterations, n + ft.batch)

@@ -12,7 +12,8 @@ closed-loop runs with the sampled PI controller, G15; steady[=dme_script|dme_nb|
 G17; profile[=A|B|C|AS|A0|C0|S]: axial profiles of catalyst activity and coolant temperature, G18; campaign[=DA|DB|DC|DI]:
 time-on-stream runs with catalyst deactivation, G19; policy[=PA|PS|PB]: the coolant policy of such a run, G20;
 sensitivity[=SA|SB|SK|SW]: parametric sensitivities of the steady state, G21; fit[=FA|FB|FN]: kinetic parameter
-estimation from steady-state data, G22; frequency[=FA|FB|FI]: frequency response of the steady state, G23 - like G13..G15 these
+estimation from steady-state data, G22; fit_ext[=FC|FP|FL|FL:<feed>]: the same with log-scaled and bounded parameters and data
+along the bed, G24; frequency[=FA|FB|FI]: frequency response of the steady state, G23 - like G13..G15 these
 run SciPy on oracle/n2_oracle.py, so the repository root must be on PYTHONPATH as well).
 The reference never travels to the GPU box; only the small .npz/.json files written here do.
 Inputs come from tests/inputs.py (this repo's restatement of the reference's test inputs).
@@ -1645,6 +1646,73 @@ def g_frequency(which=None):
               % (name, time.time() - t0, rel.max(), out["residual"]), flush=True)
 
 
+# ------------------------------------------------------------------ G24: log-scaled and bounded parameters, data along the bed
+# (solver-config "fit" with "scale", "bounds", "temperature-profile", "mole-fraction-profile").  tests/fit_ext_ref.py: FC
+# and FP by scipy.optimize.least_squares with bounds= on the oracle's steady states, polished on the face the fit ends on;
+# FL by the product's numpy law (fit.emulate_update_ex) on the oracle, at the lowest of fit_ext_ref.FL_FEEDS times the
+# notebook's feed rate at which it reaches p_true within fit_ref.TRUE_CAP in at most 30 iterations - a candidate that does
+# not is refused (SystemExit is caught per candidate, recorded under "tried", and the next one is run); fit_ext=FL:<feed>
+# runs one candidate alone.  The refusals of G22 (the gate on the steady states, COND_CAP) hold.
+def g_fit_ext(which=None):
+    import fit_ext_ref as FX
+    import fit_ref as FR
+    from oracle import n2_oracle as O
+    path = os.path.join(GOLD, "g24_fit_ext.json")
+
+    def say(msg):
+        print("G24 %s" % msg, flush=True)
+
+    def record(name, entry):
+        meta = {"cases": {}}
+        if os.path.exists(path):
+            with open(path) as fh:
+                meta = json.load(fh)
+        meta.update({"gate": FR.CR.GATE, "cond_cap": FR.COND_CAP, "true_cap": FR.TRUE_CAP, "zNo": FX.ZNO, "sigma": FX.SIGMA,
+                     "noise_seed": FX.NOISE_SEED, "on_bound": FX.ON_BOUND, "positions": list(FX.T_POSITIONS),
+                     "port": list(FX.PORT), "fl_feeds": list(FX.FL_FEEDS),
+                     "reference": "tests/fit_ext_ref.py: scipy.optimize.least_squares (trf, bounds=) on steady states of "
+                                  "oracle.n2_oracle, polished on the active face; FL: fit.emulate_update_ex on the oracle"})
+        case = meta["cases"].setdefault(name, {})
+        entry = dict(entry, tried=dict(case.get("tried", {}), **entry["tried"])) if "tried" in entry else entry
+        case.update(entry)
+        with open(path, "w") as fh:
+            json.dump(meta, fh, indent=1)
+
+    feed_only = None
+    if which and which.startswith("FL:"):
+        which, feed_only = "FL", float(which.split(":", 1)[1])
+    for name in ([which] if which else ["FC", "FP", "FL"]):
+        t0 = time.time()
+        if name == "FL":
+            tried = {}
+            for feed in ([feed_only] if feed_only else FX.FL_FEEDS):
+                try:
+                    out = FX.run_fl(O, feed, say)
+                except SystemExit as err:
+                    tried["%g" % feed] = str(err)
+                    say(str(err))
+                    record("FL", {"tried": tried})
+                    continue
+                tried["%g" % feed] = "converged in %d iterations" % out["iterations"]
+                np.savez_compressed(os.path.join(GOLD, "g24_fit_ext_FL.npz"), **{k: np.asarray(v) for k, v in out.items()})
+                record("FL", dict(FX.CASES["FL"], tried=tried, feed=float(feed), p_ref=[float(v) for v in out["p_ref"]],
+                                  iterations=int(out["iterations"]), residual=float(out["residual_gate"]),
+                                  linear_law_on_the_device="does not reach p_true from this start at 40 times the "
+                                                           "notebook's feed rate (profiles/fit.md)"))
+                say("FL written at %gx feed (%.0f s)" % (feed, time.time() - t0))
+                break
+            else:
+                raise SystemExit("G24 FL: no candidate of %s converged: %s" % (list(FX.FL_FEEDS), tried))
+            continue
+        out = FX.run_case(O, name, say)
+        np.savez_compressed(os.path.join(GOLD, "g24_fit_ext_%s.npz" % name), **{k: np.asarray(v) for k, v in out.items()})
+        record(name, dict(FX.CASES[name], p_ref=[float(v) for v in out["p_ref"]], active=[int(v) for v in out["active"]],
+                          cost=float(out["cost"]), cond=float(out["cond"]), residual=float(out["residual_gate"]),
+                          nfev=int(out["nfev"])))
+        say("%s written (%.0f s): p_ref %s, active %s, cost %.6e, scaled cond(H) %.3e, worst max|f| %.2e"
+            % (name, time.time() - t0, out["p_ref"], out["active"], out["cost"], out["cond"], out["residual_gate"]))
+
+
 def main(argv):
     os.makedirs(GOLD, exist_ok=True)
     for what in argv:
@@ -1688,6 +1756,8 @@ def main(argv):
             g_policy(what.split("=", 1)[1] if "=" in what else None)
         elif what == "sensitivity" or what.startswith("sensitivity="):
             g_sensitivity(what.split("=", 1)[1] if "=" in what else None)
+        elif what == "fit_ext" or what.startswith("fit_ext="):
+            g_fit_ext(what.split("=", 1)[1] if "=" in what else None)
         elif what == "fit" or what.startswith("fit="):
             g_fit(what.split("=", 1)[1] if "=" in what else None)
         elif what == "frequency" or what.startswith("frequency="):
